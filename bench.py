@@ -12,8 +12,13 @@ workgroup per scene) overlap the MFMA GEMMs of other passes.  Every pass still p
 scenes and every step is finalised (its per-scene detections materialised on the host side) inside the timed
 region.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, runs the timed stream and prints the headline line (`value`, `ms_per_step`, the timing description,
+`crosscheck`, `latency_under_load`).  `--dump-outputs DIR` writes the detections of the stream's last step (rank 0) as
+float32 .npy files.  Everything else described below (the cold run, the self-check, latency, roofline, CPU baseline and the
+child-process legs) runs only with `--full`.
 
 A STEP is one batch of --batch (8) scenes.  The pipeline coalesces --merge consecutive batches into one PASS (default at
 K = 20: 10 batches = 80 scenes; every kernel of the path works scene by scene, so a scene's result does not depend on what
@@ -41,7 +46,7 @@ mismatch exits non-zero.
 N > 1: one process per GPU, scenes sharded (weak scaling, 8 scenes per GPU per step), no collective on the data
 path; RCCL is used only for the barrier and the max-over-ranks of the window time.  Without torchrun
 (`WORLD_SIZE` unset) `--gpus N` starts the N rank processes itself, before anything touches the GPU.  Rank 0
-prints ONE JSON line.  N = 1 without `--worker`: an orchestrating parent that never touches the GPU starts the
+prints ONE JSON line.  N = 1 with `--full`, without `--worker`: an orchestrating parent that never touches the GPU starts the
 measuring worker and then the extra legs (dense rows, the other BASELINE configurations, ray-cast LiDAR scenes) as
 processes of their own, one at a time, and prints the merged line.  Every leg that runs on other scenes or rows (dense rows,
 ray-cast scenes, 65536-point scenes) reports its own GEMM-family roofline, the 65536-point leg its samplers' us per pick as well
@@ -62,8 +67,10 @@ import time
 # passes kept in flight serialise 4-wide.  Measured on MI355X: early in the round (24 streams) 4 queues 2051
 # scenes/s, 8 -> 2039, 16 -> 2929, 32 -> 2482; single-graph passes 16 queues / 15 streams 4372, 24 / 22 4549,
 # 32 / 24 4434; two-stage pipeline (16 main + 6 sampler streams) 24 queues 9680, 28 -> 7720, 32 -> 8140.
-# Must be set before the HIP runtime initialises.
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '24')
+# Must be set before the HIP runtime initialises.  A smaller inherited value (the runtime's default of 4 is often exported
+# explicitly) is raised: the pipeline's 22 streams would not fit, and ScenePipeline refuses to run aliased.
+if int(os.environ.get('GPU_MAX_HW_QUEUES', '0')) < 24:
+    os.environ['GPU_MAX_HW_QUEUES'] = '24'
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -109,7 +116,8 @@ def child_rate(args, env_extra, extra_args=(), note="", roofline=False):
     cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', str(args.steps), '--warmup', str(args.warmup),
            '--cpu-scenes', '0', '--no-roofline', '--no-legs', '--worker', '--batch', str(args.batch), '--points', str(args.points), '--cfg', args.cfg,
            '--streams', str(args.raw_streams), '--group', str(args.group), '--prefetch', str(args.raw_prefetch), '--merge', str(args.merge),
-           '--sampler-streams', str(args.sampler_streams), '--scene', args.scene] + (['--leg-roofline'] if roofline else []) + list(extra_args)
+           '--sampler-streams', str(args.sampler_streams), '--scene', args.scene, '--full'] + (['--leg-roofline'] if roofline else []) + list(extra_args)
+    out = None
     try:
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
         d = json.loads(out.stdout.strip().splitlines()[-1])
@@ -130,7 +138,10 @@ def child_rate(args, env_extra, extra_args=(), note="", roofline=False):
             res["note"] = note
         return res
     except Exception as e:  # noqa: BLE001
-        return {"error": repr(e)[:300]}
+        err = {"error": repr(e)[:300]}
+        if out is not None:      # a leg that printed no line: its exit status and the end of its stderr say why
+            err["rc"], err["stderr_tail"] = out.returncode, out.stderr[-600:]
+        return err
 
 
 def orchestrate(args):
@@ -258,6 +269,18 @@ def spawn_ranks(n):
     return rc
 
 
+def dump_outputs(out_dir, preds):
+    """the detections of one step as the timed path hands them to its caller (one dict per scene), concatenated over the step's
+    scenes in scene order: pred_boxes (D, box size), pred_scores (D,), pred_labels (D,), scene_counts (scenes,); float32"""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"pred_boxes": torch.cat([p['pred_boxes'] for p in preds]),
+              "pred_scores": torch.cat([p['pred_scores'] for p in preds]),
+              "pred_labels": torch.cat([p['pred_labels'] for p in preds]),
+              "scene_counts": torch.tensor([len(p['pred_scores']) for p in preds])}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a.cpu().numpy().astype(np.float32))
+
+
 def device_identity():
     pr = torch.cuda.get_device_properties(torch.cuda.current_device())
     ident = getattr(pr, 'uuid', None)
@@ -291,6 +314,9 @@ def main():
     ap.add_argument('--worker', action='store_true', help='(internal) the measuring process started by the orchestrating parent')
     ap.add_argument('--no-graph', action='store_true', help='eager launches instead of captured hipGraphs')
     ap.add_argument('--h2d', action='store_true', help='PCIe-inclusive variant: every step uploads its batch from pinned host memory (never the headline value)')
+    ap.add_argument('--full', action='store_true', help='besides the headline: cold run, self-check, latency, roofline, CPU baseline and '
+                                                        'the child-process legs (dense rows, other BASELINE configs, operating points, traffic, H2D)')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR', help='write the detections of the timed stream\'s last step to DIR/*.npy (float32)')
     args = ap.parse_args()
     # pipeline shape: coalesced passes of up to 80 scenes by default (32 for scenes of more than 16384 points: bench_legs.
     # scenes_per_pass_target; round 2 settled on 32, round 5 re-measured: scripts/r05/gpu_t14.sh .. gpu_t16.sh)
@@ -315,7 +341,7 @@ def main():
             raise SystemExit("bench.py: --gpus %d but %d visible device(s): one process per GPU (DET6D_BENCH_BACKEND=gloo allows a "
                              "dry run on shared devices)" % (args.gpus, torch.cuda.device_count()))
         raise SystemExit(spawn_ranks(args.gpus))       # nothing above has initialised HIP
-    if 'WORLD_SIZE' not in os.environ and not args.worker and not args.no_legs:
+    if 'WORLD_SIZE' not in os.environ and args.full and not args.worker and not args.no_legs:
         raise SystemExit(orchestrate(args))            # legs run in processes of their own, one at a time (see orchestrate)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -435,7 +461,7 @@ def main():
     tail = capacity
     first = preroll + args.warmup - 1
     last = first + (n_windows - 1) * k + args.steps
-    stamps, dets, issued = {}, [0], {}
+    stamps, dets, issued, final = {}, [0], {}, [None]
     device_clock = not args.no_graph       # completion times from the device (one timing event per pass) instead of the host
 
     def on_done(step, r, preds):
@@ -445,8 +471,9 @@ def main():
                 issued[step] = r.issued_at
         if first < step <= first + args.steps:
             dets[0] += sum(len(p['pred_scores']) for p in preds)
+        final[0] = preds                   # steps arrive in order: the stream's last step stays (views, read before any relaunch)
 
-    sampler = ClockPowerSampler() if (rank == 0 and world == 1) else None     # shader clock + socket power over the stream
+    sampler = ClockPowerSampler() if (args.full and rank == 0 and world == 1) else None     # shader clock + socket power over the stream
     bracket()
     GraphedDet6D.host_wait_s = 0.0
     GraphedDet6D.stamp_launches = device_clock
@@ -458,6 +485,8 @@ def main():
     run(last + 1 + tail, on_done)
     bracket()
     t_stream = time.perf_counter() - t_stream
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, final[0])
     # (the pipeline's fill and the pre-roll are left out: the first quarter of the stream)
     clocks = sampler.stop(t_wall0 + 0.25 * t_stream, t_wall0 + t_stream) if sampler is not None else None
     GraphedDet6D.stamp_launches = False
@@ -496,25 +525,28 @@ def main():
                   "note": "fit = least-squares slope of in-order delivery time over step index across the windows' span; whole stream = "
                           "all %d steps over the host clock between the two barriers (fill + drain inside); per-rank figures x ranks" % (last + 1 + tail)}
 
-    # ---- cold: K steps on an EMPTY pipeline, synchronize on both sides (fill + drain inside) ----------------------------
-    bracket()
-    t0 = time.perf_counter()
-    run(args.steps)
-    bracket()
-    cold = time.perf_counter() - t0
+    # ---- cold (--full): K steps on an EMPTY pipeline, synchronize on both sides (fill + drain inside) -------------------
+    cold = None
+    if args.full:
+        bracket()
+        t0 = time.perf_counter()
+        run(args.steps)
+        bracket()
+        cold = time.perf_counter() - t0
 
     per_rank = [round(args.steps * b / elapsed_own, 1)]
     if dist is not None:
         dev = 'cuda' if dist.get_backend() == 'nccl' else 'cpu'
-        t = torch.tensor([elapsed, cold], dtype=torch.float64, device=dev)
+        t = torch.tensor([elapsed, cold or 0.0], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, cold = float(t[0].item()), float(t[1].item())
+        elapsed = float(t[0].item())
+        cold = float(t[1].item()) if cold is not None else None
         per_rank = [None] * world
         dist.all_gather_object(per_rank, round(args.steps * b / elapsed_own, 1))
 
-    # ---- self-check: what was timed is what the eager model computes ------------------------------------------------------
+    # ---- self-check (--full): what was timed is what the eager model computes ---------------------------------------------
     check = "skipped"
-    if pipe is not None and not args.h2d:
+    if args.full and pipe is not None and not args.h2d:
         bad, total = selfcheck(model, pipe, b)
         check = "ok" if not bad else "MISMATCH in (pass, scene) %s" % bad[:8]
         if rank == 0 or bad:
@@ -562,12 +594,13 @@ def main():
             "ranks_seen": ranks_seen, "per_rank_scenes_per_s": per_rank,
             "crosscheck": crosscheck, "stream_total_s": round(t_stream, 4), "host_blocked_frac": round(host_wait / t_stream, 3),
             "detections_in_window": dets[0],
-            "cold": {"scenes_per_s": round(world * args.steps * b / cold, 2), "ms_per_step": round(cold / args.steps * 1e3, 4),
-                     "note": "the same %d steps on an empty pipeline, barrier+synchronize on both sides: pipeline fill + drain included" % args.steps},
         }
+        if cold is not None:
+            line["cold"] = {"scenes_per_s": round(world * args.steps * b / cold, 2), "ms_per_step": round(cold / args.steps * 1e3, 4),
+                            "note": "the same %d steps on an empty pipeline, barrier+synchronize on both sides: pipeline fill + drain included" % args.steps}
         if latency_under_load is not None:
             line["latency_under_load"] = latency_under_load
-        if world == 1:
+        if world == 1 and args.full:
             # Both runners are built BEFORE either is timed and freed after both: releasing a captured graph (its memory pool,
             # its queues) right before a measurement inflates it (scripts/r04/latency_b1_ctx.py: 3.35 -> 3.7 ms after `del`
             # of one runner, 13 ms for the first frame after a pipeline was freed).  Medians over the timed launches.
@@ -598,7 +631,7 @@ def main():
             line["config"]["latency_b1_ms_per_frame"] = line["latency_b1"]["ms_per_frame"]
             line["config"]["latency_ms_per_batch"] = line["latency"]["ms_per_batch"]
             del lat, lat1, one
-        if world == 1 and not args.no_roofline:
+        if world == 1 and args.full and not args.no_roofline:
             line["roofline"] = linear_roofline(model, pass_inputs[0], b * merge, flops, streams=MAIN_STREAMS)
             line["roofline"]["scenes_per_pass"] = b * merge
             line["roofline"]["steps_per_pass"] = merge
@@ -609,7 +642,7 @@ def main():
             pipe = None  # noqa: F841  (frees the captured graphs before the pipeline leg builds its own)
             torch.cuda.empty_cache()
             line["pipeline"] = pipeline_rate(cfg, model, b * merge, n, group=args.group, n_main=depth, prefetch=args.prefetch)
-        elif world == 1 and args.leg_roofline:
+        elif world == 1 and args.full and args.leg_roofline:
             line["roofline"] = linear_roofline(model, pass_inputs[0], b * merge, flops, streams=MAIN_STREAMS,
                                                pmc_tag='65536' if n == 65536 else args.scene)
             line["roofline"]["scenes_per_pass"] = b * merge
@@ -617,11 +650,11 @@ def main():
             line["compact_fill"] = compact_fill(model, points, b)
             if n != 16384:               # the samplers / queries of this leg's shapes (the 65536-point cooperative sampler)
                 line["index_kernels"] = index_kernel_rates(model, points, b, n)
-        elif world == 1:
+        elif world == 1 and args.full:
             line["compact_fill"] = compact_fill(model, points, b)
         if clocks:
             line["clocks"] = {"sclk_mhz": clocks["sclk_mhz"], "power_w": clocks["power_w"]}
-        if world == 1 and args.cpu_scenes > 0:
+        if world == 1 and args.full and args.cpu_scenes > 0:
             line["cpu_baseline"] = cpu_baseline(cfg, model, pts_np, args.cpu_scenes)
         print(json.dumps(line), flush=True)
     if dist is not None:

@@ -509,7 +509,7 @@ def measured_traffic(bench_path, extra_args=(), passes=3, timeout=420, scenes_pe
         try:
             cmd = ['rocprofv3', '--kernel-trace', '--pmc', ctr, '--output-format', 'csv', '-d', d, '-o', 'pmc', '--',
                    sys.executable, bench_path, '--gpus', '1', '--steps', str(passes + 2), '--warmup', '2', '--batch', str(scenes_per_pass), '--streams', '1',
-                   '--no-graph', '--cpu-scenes', '0', '--no-roofline', '--no-legs', '--worker', '--preroll', '0', '--windows', '1'] + list(extra_args)
+                   '--no-graph', '--cpu-scenes', '0', '--no-roofline', '--no-legs', '--worker', '--preroll', '0', '--windows', '1', '--full'] + list(extra_args)
             env = dict(os.environ, TMPDIR=os.environ.get('TMPDIR', '/tmp'))
             out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout, cwd=d)
             files = glob.glob(os.path.join(d, '**', '*counter_collection.csv'), recursive=True)

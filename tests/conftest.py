@@ -11,7 +11,9 @@ if ROOT not in sys.path:
 # 24 hardware queues.  ROCm reads GPU_MAX_HW_QUEUES once, when the HIP runtime initialises, so it is exported here, before any
 # test module can touch the GPU (round 4's GPU run had the default 4 queues: the streams aliased and serialised).  Importing
 # the package does the same for any other caller (de6d_amd/__init__.py); ScenePipeline raises when fewer queues are in effect.
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '24')
+# A smaller inherited value (the runtime's default of 4 is often exported explicitly) is raised to 24 here, as bench.py does.
+if int(os.environ.get('GPU_MAX_HW_QUEUES', '0')) < 24:
+    os.environ['GPU_MAX_HW_QUEUES'] = '24'
 import de6d_amd  # noqa: E402,F401
 
 

@@ -6,6 +6,8 @@ writes are data (inputs + expected outputs) and are what travels to the GPU box.
 
   nms_ref.npz      (boxes, thr) -> IoU matrices from the reference's OWN iou3d_cpu.cpp (oracle/_ref)
                    + keep lists from the greedy scan of iou3d_nms.cpp:116-132 applied to them
+  ref_iou.npz      the same iou3d_cpu.cpp on the inputs of test_oracle_ref.py (IoU matrices) and test_nms_filter.py
+                   (IoU > 0 bit masks of every box family, with a digest of its inputs)
   box_coder.npz    (code, points) -> boxes9 from the reference's PointBinResidual6DCoder.decode_torch
                    (core/pcdet/utils/box_coder_utils.py imported standalone)
   producer.npz     raw frames -> ids chosen by the reference's OWN DataProcessor
@@ -100,6 +102,28 @@ def gen_nms():
             out["rmargin_%d_%s" % (c, tag)] = np.float32(np.abs(off - np.float32(thr)).min())
     np.savez_compressed(os.path.join(HERE, "nms_ref.npz"), **out)
     print("nms_ref.npz", len(out), "arrays")
+
+
+def gen_ref_iou():
+    """ref_iou.npz: the reference's iou3d_cpu.cpp (oracle/_ref) on the inputs of tests/test_oracle_ref.py (IoU matrices) and
+    of tests/test_nms_filter.py (per family: which pairs have IoU > 0, as a packed bit mask, and a digest of the inputs)"""
+    from tests import test_oracle_ref as t_ref
+    from tests import test_nms_filter as t_filter
+    out = {}
+    for seed, k, spread in t_ref.CASES:
+        boxes = random_boxes(seed, k, spread=spread)
+        out["boxes_%d" % seed], out["iou_%d" % seed] = boxes, oref.boxes_iou_bev_cpu(boxes, boxes)
+    boxes = t_ref.degenerate_boxes()
+    out["boxes_degenerate"], out["iou_degenerate"] = boxes, oref.boxes_iou_bev_cpu(boxes, boxes)
+    rng = np.random.default_rng(t_filter.SEED)
+    for rep in range(t_filter.REPS):
+        for f, (name, a, b) in enumerate(t_filter.families(rng)):
+            with np.errstate(invalid='ignore'):
+                positive = oref.boxes_iou_bev_cpu(a, b) > 0        # NaN > 0 is False, as in the mask kernel's `iou > thresh`
+            out["filter_positive_%d_%d" % (rep, f)] = np.packbits(positive.ravel())
+            out["filter_digest_%d_%d" % (rep, f)] = np.array(t_filter.inputs_digest(a, b))
+    np.savez_compressed(os.path.join(HERE, "ref_iou.npz"), **out)
+    print("ref_iou.npz", len(out), "arrays")
 
 
 # ----------------------------------------------------------------------------- box coder
@@ -751,7 +775,7 @@ if __name__ == "__main__":
         sys.exit(0)
     oops.build()
     assert oref.available(), "build oracle/_ref first: make -C oracle _ref"
-    gens = dict(nms=gen_nms, box_coder=gen_box_coder, model=gen_model, producer=gen_producer, annos=gen_annos,
+    gens = dict(nms=gen_nms, ref_iou=gen_ref_iou, box_coder=gen_box_coder, model=gen_model, producer=gen_producer, annos=gen_annos,
                 slope=gen_slope, eval=gen_eval, model_full=gen_model_full, model_full_other=gen_model_full_other, model_full_65536=gen_model_full_65536, fp=gen_fp,
                 extension_api=gen_extension_api)
     for name in (sys.argv[1:] or list(gens)):      # `python make_golden.py model_full` regenerates one fixture

@@ -1,16 +1,21 @@
 """The separated-pair rule of the NMS mask kernels (csrc/iou3d_nms.hip: d6_nms_radius / d6_nms_near) against the REFERENCE's own
-iou3d_cpu.cpp (oracle/_ref): a pair the rule skips must never have an IoU above 0 in the reference's arithmetic — so skipping it
+iou3d_cpu.cpp (its IoU > 0 masks on these families: tests/golden/ref_iou.npz, make_golden.py: gen_ref_iou): a pair the rule skips
+must never have an IoU above 0 in the reference's arithmetic — so skipping it
 cannot change a suppression bit (`iou > thresh`, thresh >= 0).  Random scenes and the adversarial families the argument in the
 kernel's comment worries about: rows of collinear axis-aligned boxes, rows sharing a rotated heading, huge coordinates, tiny and
 degenerate boxes, pairs right at the rule's boundary."""
+import hashlib
+import os
+
 import numpy as np
-import pytest
 
-from oracle import ref as oref
-
-pytestmark = pytest.mark.skipif(not oref.available(), reason="oracle/_ref (the reference's iou3d_cpu.cpp) is not built here")
-
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'ref_iou.npz')
+SEED, REPS = 20261003, 3
 f32 = np.float32
+
+
+def inputs_digest(a, b):
+    return hashlib.sha256(a.tobytes() + b.tobytes()).hexdigest()
 
 
 def nms_radius(b):
@@ -83,15 +88,18 @@ def families(rng):
 
 
 def test_skipped_pairs_have_no_overlap_in_the_reference():
-    rng = np.random.default_rng(20261003)
+    ref = np.load(GOLDEN)
+    rng = np.random.default_rng(SEED)
     skipped = evaluated = 0
-    for rep in range(3):
-        for name, a, b in families(rng):
-            iou = oref.boxes_iou_bev_cpu(a, b)
+    for rep in range(REPS):
+        for f, (name, a, b) in enumerate(families(rng)):
+            key = '%d_%d' % (rep, f)
+            assert inputs_digest(a, b) == str(ref['filter_digest_' + key]), "%s: not the inputs of the stored reference masks" % name
+            # the reference's iou > 0 (NaN > 0 is False: what `iou > thresh` gives in the mask kernel too)
+            positive = np.unpackbits(ref['filter_positive_' + key], count=a.shape[0] * b.shape[0]).reshape(a.shape[0], b.shape[0])
             near = nms_near(a, b)
-            with np.errstate(invalid='ignore'):
-                bad = (~near) & (iou > 0)                  # NaN > 0 is False: what `iou > thresh` gives in the mask kernel too
-            assert not bad.any(), "%s: the rule skips a pair with IoU %r" % (name, iou[bad][:5])
+            bad = (~near) & (positive == 1)
+            assert not bad.any(), "%s: the rule skips pairs with IoU > 0 %r" % (name, np.argwhere(bad)[:5].tolist())
             skipped += int((~near).sum())
             evaluated += int(near.sum())
     # the rule is worth having: most pairs are skipped, and the test saw millions of them

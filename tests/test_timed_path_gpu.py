@@ -299,7 +299,7 @@ def test_bench_entry_point_checks_itself():
     `selfcheck: ok` (every pass compared with the eager model inside the bench), cold / latency keys"""
     import json
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '8', '--warmup', '2', '--worker',
-                          '--no-legs', '--no-roofline', '--cpu-scenes', '0', '--windows', '3', '--preroll', '1'],
+                          '--no-legs', '--no-roofline', '--cpu-scenes', '0', '--windows', '3', '--preroll', '1', '--full'],
                          cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
@@ -311,6 +311,28 @@ def test_bench_entry_point_checks_itself():
     assert d['selfcheck'] == 'ok' and d['steps'] == 8 and d['n_gpus'] == 1 and d['dtype'] == 'f32' and d['value'] > 0
     assert 'steady-state' in d['config']['timing'] and d['config']['points_per_scene'] == 16384
     assert d['config']['batches_per_pass'] == 8 and d['config']['scenes_per_pass'] == 64      # 8 steps = one coalesced pass
+
+
+def test_plain_bench_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the timed stream and the headline line only (no orchestrated legs,
+    cold run, self-check or roofline); --dump-outputs writes the last step's detections as float32 arrays"""
+    import json
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '8', '--warmup', '2',
+                          '--windows', '3', '--preroll', '1', '--dump-outputs', str(tmp_path)],
+                         cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'steps', 'warmup'):
+        assert key in d, key
+    assert d['steps'] == 8 and d['value'] > 0 and d['ms_per_step'] > 0 and d['config']['hw_queues'] >= 24
+    for key in ('cold', 'latency', 'roofline', 'cpu_baseline', 'dense_rows', 'other_configs'):
+        assert key not in d, key
+    z = {name: np.load(str(tmp_path / (name + '.npy'))) for name in ('pred_boxes', 'pred_scores', 'pred_labels', 'scene_counts')}
+    assert all(a.dtype == np.float32 for a in z.values())
+    assert z['scene_counts'].shape == (8,) and z['pred_boxes'].shape[0] == z['pred_scores'].shape[0] == z['pred_labels'].shape[0]
+    assert z['scene_counts'].sum() == z['pred_scores'].shape[0] > 0
 
 
 @pytest.mark.parametrize("scene,merge", [("beam", 4), ("uniform", 4), ("uniform", 10), ("beam", 10)])

@@ -10,6 +10,9 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libdet6d_hip.so")
+#: the extension library (include/det6d_ext.h): entry points without an oracle twin, each with a CPU model under tests/models/
+EXT_LIB = os.path.join(CSRC, "libdet6d_hip_ext.so")
+EXT_DIR = os.path.join(CSRC, "ext")
 SOURCES = ["runtime.hip", "fps.hip", "fps_cells.hip", "fps_seq.hip", "fps_coop.hip", "ball_query.hip", "ball_query_grid.hip", "points.hip", "iou3d_nms.hip", "iou3d_host.hip", "linear.hip", "mlp_chain.hip", "mlp_group.hip", "mlp_rows.hip", "compact.hip", "expand.hip", "prepare.hip", "annos.hip", "slope.hip", "kitti_eval.hip"]
 #: kernels that exist only in the -DDET6D_EXPERIMENTS library (measured alternatives that did not earn their place)
 EXPERIMENT_SOURCES = []
@@ -42,22 +45,32 @@ def _stale(out, deps):
 
 
 def build(force=False, verbose=False, experiments=False, knobs=False):
-    """experiments=True: a SEPARATE library (libdet6d_hip_experiments.so) compiled with -DDET6D_EXPERIMENTS, in which the
+    """Builds libdet6d_hip.so and, beside it, libdet6d_hip_ext.so (csrc/ext/*.hip); returns the main library's path.
+    experiments=True: a SEPARATE library (libdet6d_hip_experiments.so) compiled with -DDET6D_EXPERIMENTS, in which the
     tile-sweep / timing / stand-in environment variables of scripts/experiments are live.  The shipped library ignores them."""
     # knobs=True: a third library (libdet6d_hip_knobs.so, -DDET6D_KNOBS): the shipped kernels with the route / tile switches
     # live and no instrumentation — the flavour A/B runs of routes are taken in (csrc/common.h)
     objdir = os.path.join(CSRC, "build_experiments" if experiments else "build_knobs" if knobs else "build")
-    os.makedirs(objdir, exist_ok=True)
-    hipcc = _hipcc()
     flags = FLAGS + (["-DDET6D_EXPERIMENTS"] if experiments else ["-DDET6D_KNOBS"] if knobs else [])
     lib = LIB.replace(".so", "_experiments.so") if experiments else LIB.replace(".so", "_knobs.so") if knobs else LIB
-
     sources = SOURCES + (EXPERIMENT_SOURCES if experiments else [])
+    out = _link(CSRC, sources, objdir, flags, lib, HEADERS, force, verbose)
+    if not (experiments or knobs):
+        ext_sources = sorted(f for f in os.listdir(EXT_DIR) if f.endswith(".hip"))
+        _link(EXT_DIR, ext_sources, os.path.join(objdir, "ext"), flags, EXT_LIB,
+              HEADERS + [os.path.join(HERE, "..", "include", "det6d_ext.h")], force, verbose)
+    return out
+
+
+def _link(srcdir, sources, objdir, flags, lib, headers, force, verbose):
+    """compile `sources` (relative to srcdir) into objdir, link them into `lib`, merge their resource reports"""
+    os.makedirs(objdir, exist_ok=True)
+    hipcc = _hipcc()
 
     def compile_one(src):
-        s = os.path.join(CSRC, src)
+        s = os.path.join(srcdir, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
-        if force or _stale(o, [s] + HEADERS):
+        if force or _stale(o, [s] + headers):
             # the compiler's per-kernel resource report goes to <object>.usage.json (tests/test_build_resources.py: the
             # latency-chain kernels must not touch scratch memory — round 4 lost 20 % of a sampler to an array the compiler
             # had quietly moved there)

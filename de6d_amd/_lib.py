@@ -179,6 +179,47 @@ def lib():
     return _lib
 
 
+#: libdet6d_hip_ext.so (include/det6d_ext.h): entry points without an oracle twin ("The extension library")
+EXT_LIB_PATH = os.path.join(_HERE, "csrc", "libdet6d_hip_ext.so")
+_EXT_SIGNATURES = {
+    "det6d_ext_fps_features": [c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_float, _P, c_int64, _P, c_int, c_int, c_int, _P],
+    "det6d_ext_fps_matrix": [c_int, c_int, c_int, _P, _P, _P, _P],
+}
+#: every symbol include/det6d_ext.h declares (tests/test_ext_boundary.py checks the export table)
+EXT_EXPORTED_SYMBOLS = sorted(list(_EXT_SIGNATURES) + ["det6d_ext_version", "det6d_ext_last_error",
+                                                          "det6d_ext_fps_features_workspace_bytes"])
+_ext_lib = None
+
+
+def ext_lib():
+    """Load libdet6d_hip_ext.so (built beside libdet6d_hip.so by de6d_amd._build)."""
+    global _ext_lib
+    if _ext_lib is None:
+        lib()
+        if not os.path.exists(EXT_LIB_PATH):
+            raise Det6dError("libdet6d_hip_ext.so is missing (%s). Build it with `python -m de6d_amd._build`; there is no "
+                             "CPU/PyTorch fallback." % EXT_LIB_PATH)
+        handle = ctypes.CDLL(EXT_LIB_PATH)
+        for name, argtypes in _EXT_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.argtypes = argtypes
+            fn.restype = c_int
+        handle.det6d_ext_version.restype = ctypes.c_char_p
+        handle.det6d_ext_last_error.restype = ctypes.c_char_p
+        handle.det6d_ext_fps_features_workspace_bytes.argtypes = [c_int, c_int]
+        handle.det6d_ext_fps_features_workspace_bytes.restype = c_int64
+        _ext_lib = handle
+    return _ext_lib
+
+
+def call_ext(name, *args):
+    """Invoke an entry point of the extension library; raises on any negative status."""
+    rc = getattr(ext_lib(), name)(*args)
+    if rc < 0:
+        raise Det6dError("%s failed: rc=%d %s" % (name, rc, ext_lib().det6d_ext_last_error().decode()))
+    return rc
+
+
 def version():
     return lib().det6d_version().decode()
 

@@ -22,7 +22,7 @@ import os
 import torch
 import torch.nn as nn
 
-from ....ops_backend import fused, pointnet2_batch_hip as pn2
+from ....ops_backend import ffps, fused, pointnet2_batch_hip as pn2
 from . import pointnet2_utils
 
 
@@ -172,20 +172,25 @@ class _PointnetSAModuleFSBase(nn.Module):
         return self._folded
 
     # ---- sampling -----------------------------------------------------------------------
-    def _sample_one(self, xyz, scores, lo, hi, method, npoint, idx_out, offset):
+    def _sample_one(self, xyz, scores, lo, hi, method, npoint, idx_out, offset, rows=None):
         """one sampler -> idx_out[:, offset:offset+npoint]; slice, sigmoid**gamma weights, 1e10 init and
-        the + lo offset (pointnet2_modules.py:380,415-424,448) all happen inside det6d_fps_fused"""
+        the + lo offset (pointnet2_modules.py:380,415-424,448) all happen inside det6d_fps_fused (d-fps, s-fps) or
+        det6d_ext_fps_features (f-fps: cdist(xyz) + cdist(features) * gamma over the layer's rows,
+        pointnet2_modules.py:382-387)"""
         hi = xyz.shape[1] if hi == -1 else hi
         if method == 'd-fps':
             fused.fps_fused(xyz, lo, hi, npoint, None, 1.0, idx_out, offset)
         elif method == 's-fps':
             assert scores is not None
             fused.fps_fused(xyz, lo, hi, npoint, scores, self.weight_gamma, idx_out, offset)
+        elif method == 'f-fps':
+            assert rows is not None, "f-fps samples on the layer's rows [xyz | features]"
+            ffps.fps_features(rows, self.in_channels, npoint, self.weight_gamma, lo, hi, idx_out, offset)
         else:
             raise NotImplementedError(
                 "sampling method %r is outside the Det6D hot path (SURVEY.md 2.1 #8)" % method)
 
-    def _sample(self, xyz, scores):
+    def _sample(self, xyz, scores, rows=None):
         """fusion sampling (pointnet2_modules.py:376-450).  The samplers of one layer are independent
         latency chains on one workgroup per scene, so they run concurrently on forked HIP streams
         (also under hipGraph capture, where the fork/join becomes two parallel branches)."""
@@ -209,7 +214,7 @@ class _PointnetSAModuleFSBase(nn.Module):
             for j, (((lo, hi), method, npoint), off) in enumerate(zip(jobs, offsets)):
                 if ctl is not None and ctl.hoisted(layer, j):
                     continue          # launched by the group for all its passes, ahead of this segment (runtime.hoist_plan)
-                self._sample_one(xyz, scores, lo, hi, method, npoint, idx, off)
+                self._sample_one(xyz, scores, lo, hi, method, npoint, idx, off, rows)
             if ctl is not None:
                 ctl.after_samplers(layer, xyz, idx)    # single-graph passes: fork / join of the input-only sampler chain
             return idx
@@ -220,9 +225,9 @@ class _PointnetSAModuleFSBase(nn.Module):
             side = self._side_streams[i - 1]
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                self._sample_one(xyz, scores, lo, hi, method, npoint, idx, offsets[i])
+                self._sample_one(xyz, scores, lo, hi, method, npoint, idx, offsets[i], rows)
         (lo, hi), method, npoint = jobs[0]
-        self._sample_one(xyz, scores, lo, hi, method, npoint, idx, 0)
+        self._sample_one(xyz, scores, lo, hi, method, npoint, idx, 0, rows)
         for side in self._side_streams[:len(jobs) - 1]:
             main.wait_stream(side)
         return idx
@@ -240,7 +245,7 @@ class _PointnetSAModuleFSBase(nn.Module):
         b, n, _ = xyz.shape
         new_rows = None
         if new_xyz is None:
-            sample_idx = self._sample(xyz, scores)
+            sample_idx = self._sample(xyz, scores, rows)
             m = sample_idx.shape[1]
             if f['agg'] is not None:  # next level's rows: xyz now, features by the aggregation GEMM, pad zeroed
                 ld_next = rows_ld(f['out_channels'])

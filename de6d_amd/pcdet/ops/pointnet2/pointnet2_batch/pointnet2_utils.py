@@ -9,7 +9,7 @@ import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from ....ops_backend import pointnet2_batch_hip as pointnet2
+from ....ops_backend import ffps, pointnet2_batch_hip as pointnet2
 
 
 def _i32(*shape, device):
@@ -37,6 +37,23 @@ class FarthestPointSampling(Function):
 
 
 farthest_point_sample = furthest_point_sample = FarthestPointSampling.apply
+
+
+@torch.no_grad()
+def calc_dist_matrix_for_sampling(xyz: torch.Tensor, features: torch.Tensor = None, gamma: float = 1.0):
+    """(B, N, N) = cdist(xyz, xyz) + cdist(features, features) * gamma (pointnet2_utils.py:37-44): the matrix of the
+    reference's f-fps.  The SA layers never build it: det6d_ext_fps_features computes the row of each pick on the fly."""
+    dist = torch.cdist(xyz, xyz)
+    if features is not None:
+        dist += torch.cdist(features, features) * gamma
+    return dist
+
+
+@torch.no_grad()
+def furthest_point_sample_matrix(matrix: torch.Tensor, npoint: int) -> torch.Tensor:
+    """FPS on a (B, N, N) distance matrix (pointnet2_utils.py:67-86): temp filled with 1e10, (B, npoint) int32"""
+    assert matrix.is_contiguous()
+    return ffps.fps_matrix(matrix, npoint)
 
 
 class FurthestPointSamplingWeights(Function):

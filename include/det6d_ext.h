@@ -1,0 +1,48 @@
+/*
+ * det6d_ext.h — C ABI of libdet6d_hip_ext.so, the extension library of entry points that have no twin in the CPU oracle
+ * (oracle/libdet6d_oracle.so).  Each of them comes with an executable CPU model under tests/models/ instead
+ * ("The extension library").  Conventions are those of det6d_ops.h: device pointers, caller-owned buffers,
+ * asynchronous on `stream`, DET6D_OK or a negative DET6D_E* code, never exit().
+ */
+#ifndef DET6D_EXT_H
+#define DET6D_EXT_H
+
+#include "det6d_ops.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* library identification: "det6d-hip-ext gfx950 <abi-version>" */
+const char *det6d_ext_version(void);
+/* last error seen by this library on the calling thread: a bad argument or a failed launch ("" if none) */
+const char *det6d_ext_last_error(void);
+
+/* ------------------------------------------------------------------ F-FPS --------------- */
+
+/* F-FPS: farthest point sampling on the fused distance d(i, j) = cdist(xyz)(i, j) + cdist(features)(i, j) * gamma of the
+ * reference's f-fps sampler (pointnet2_modules.py:382-387 -> pointnet2_utils.py:37-44 + sampling_gpu.cu:268-373), without
+ * the B x n x n matrix.  Points are rows [x, y, z, f_0 .. f_{c-1}, pad] of `rows` (b, n_total, ld); scene s samples m points
+ * of its slice [lo, hi) and writes pick + lo + idx_bias to idx[s * idx_stride + idx_offset + r] (r = 0 .. m-1).
+ * Arithmetic (exact, tests/models/ffps.py): |v|^2 a sequential sum of rounded squares in channel order; G(i, j) one
+ * ascending fmaf chain from 0 over (-2 v_i) . v_j, then + |v_i|^2, then + |v_j|^2 (i = the last pick, j = the candidate);
+ * d = sqrtf(clamp(G_xyz)) + sqrtf(clamp(G_feat)) * gamma, clamp(g) = g <= 0 ? 0 : g (NaN stays NaN); the reference's
+ * selection rule (first pick 0, min-distances from 1e10, d2 = fminf(d, temp), strict > per thread, halving tree).
+ * Limits: 1 <= hi - lo <= 16384, 0 <= c <= 256, c + 3 <= ld, ld % 4 == 0, `rows` 16-byte aligned, m >= 0.
+ * `workspace` holds at least det6d_ext_fps_features_workspace_bytes(b, hi - lo) bytes; its last b * 128 bytes are, after
+ * the launch, uint32 counters [b][16 waves][2]: point-rounds whose feature row was read, and wave-rounds that read any. */
+long long det6d_ext_fps_features_workspace_bytes(int b, int n);
+int det6d_ext_fps_features(int b, int n_total, int lo, int hi, int m, const float *rows, int ld, int c, float gamma,
+                           void *workspace, long long ws_bytes, int *idx, int idx_stride, int idx_offset, int idx_bias,
+                           det6d_stream_t stream);
+
+/* furthest_point_sampling_matrix_wrapper(b, n, m, matrix, temp, idx) (sampling.cpp -> sampling_gpu.cu:268-373): FPS on a
+ * caller-supplied (b, n, n) distance matrix; temp (b, n) holds the initial min-distances (the reference fills 1e10) and the
+ * final ones afterwards; idx (b, m).  The selection core of det6d_ext_fps_features.  1 <= n <= 16384, m >= 0. */
+int det6d_ext_fps_matrix(int b, int n, int m, const float *matrix, float *temp, int *idx, det6d_stream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* DET6D_EXT_H */

@@ -58,7 +58,8 @@ def build(force=False, verbose=False, experiments=False, knobs=False):
     if not (experiments or knobs):
         ext_sources = sorted(f for f in os.listdir(EXT_DIR) if f.endswith(".hip"))
         _link(EXT_DIR, ext_sources, os.path.join(objdir, "ext"), flags, EXT_LIB,
-              HEADERS + [os.path.join(HERE, "..", "include", "det6d_ext.h")], force, verbose)
+              HEADERS + [os.path.join(HERE, "..", "include", "det6d_ext.h"), os.path.join(EXT_DIR, "ext_common.h")],
+              force, verbose)
     return out
 
 

@@ -1,0 +1,6 @@
+// ext_common.h — what the sources of libdet6d_hip_ext.so share besides csrc/common.h: the library's error slot
+// (det6d_ext_last_error) is written through det6d_ext_fail, defined once in fps_features.hip.
+#pragma once
+
+// formats the message of a refused call into the calling thread's error slot; returns DET6D_EINVAL
+int det6d_ext_fail(const char *fmt, ...) __attribute__((format(printf, 1, 2)));

@@ -18,6 +18,7 @@
 #include "../common.h"
 #include "../fps_multi.h"
 #include "../../../include/det6d_ext.h"
+#include "ext_common.h"
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -300,7 +301,15 @@ void det6d_set_error(const char *what, hipError_t err) {
   snprintf(g_ext_err, sizeof(g_ext_err), "%s: %s", what, hipGetErrorString(err));
 }
 
-DET6D_API const char *det6d_ext_version(void) { return "det6d-hip-ext gfx950 ext1"; }
+int det6d_ext_fail(const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_ext_err, sizeof(g_ext_err), fmt, ap);
+  va_end(ap);
+  return DET6D_EINVAL;
+}
+
+DET6D_API const char *det6d_ext_version(void) { return "det6d-hip-ext gfx950 ext2"; }
 DET6D_API const char *det6d_ext_last_error(void) { return g_ext_err; }
 
 DET6D_API long long det6d_ext_fps_features_workspace_bytes(int b, int n) {

@@ -22,7 +22,7 @@ import os
 import torch
 import torch.nn as nn
 
-from ....ops_backend import ffps, fused, pointnet2_batch_hip as pn2
+from ....ops_backend import ffps, fused, pointnet2_batch_hip as pn2, sort_samplers
 from . import pointnet2_utils
 
 
@@ -176,7 +176,9 @@ class _PointnetSAModuleFSBase(nn.Module):
         """one sampler -> idx_out[:, offset:offset+npoint]; slice, sigmoid**gamma weights, 1e10 init and
         the + lo offset (pointnet2_modules.py:380,415-424,448) all happen inside det6d_fps_fused (d-fps, s-fps) or
         det6d_ext_fps_features (f-fps: cdist(xyz) + cdist(features) * gamma over the layer's rows,
-        pointnet2_modules.py:382-387)"""
+        pointnet2_modules.py:382-387) or det6d_ext_topk_scores (c-fps: the npoint highest weights in descending order, ties
+        by ascending index, pointnet2_modules.py:425-430).  df-fps (pointnet2_modules.py:389-414) is two launches:
+        det6d_ext_pillar_weights (counted per scene), then the weighted FPS on the slice."""
         hi = xyz.shape[1] if hi == -1 else hi
         if method == 'd-fps':
             fused.fps_fused(xyz, lo, hi, npoint, None, 1.0, idx_out, offset)
@@ -186,6 +188,11 @@ class _PointnetSAModuleFSBase(nn.Module):
         elif method == 'f-fps':
             assert rows is not None, "f-fps samples on the layer's rows [xyz | features]"
             ffps.fps_features(rows, self.in_channels, npoint, self.weight_gamma, lo, hi, idx_out, offset)
+        elif method == 'c-fps':
+            assert scores is not None
+            sort_samplers.topk_scores(scores, npoint, self.weight_gamma, lo, hi, idx_out, offset)
+        elif method == 'df-fps':
+            sort_samplers.pillar_density_fps(xyz, npoint, lo, hi, idx_out, offset)
         else:
             raise NotImplementedError(
                 "sampling method %r is outside the Det6D hot path (SURVEY.md 2.1 #8)" % method)

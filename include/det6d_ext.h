@@ -41,6 +41,35 @@ int det6d_ext_fps_features(int b, int n_total, int lo, int hi, int m, const floa
  * final ones afterwards; idx (b, m).  The selection core of det6d_ext_fps_features.  1 <= n <= 16384, m >= 0. */
 int det6d_ext_fps_matrix(int b, int n, int m, const float *matrix, float *temp, int *idx, det6d_stream_t stream);
 
+/* ------------------------------------------------------------------ C-FPS --------------- */
+
+/* C-FPS: the m points of a slice with the highest sigmoid(score) ** gamma, in descending order — the reference's
+ * scores_slice.sigmoid() ** WEIGHT_GAMMA followed by .topk(npoint) (pointnet2_modules.py:425-430).  Scene s ranks the slice
+ * [lo, hi) of `scores` (b, n_total) and writes k + lo + idx_bias to idx[s * idx_stride + idx_offset + r] (r = 0 .. m-1).
+ * Weights: w[k] = d6_sigmoid_powf(scores[s, lo + k], gamma) (det6d_math.h), the bits S-FPS sees.
+ * Order (exact, tests/models/score_topk.py): larger w first; NaN counts as larger than every number, as in torch.topk; among
+ * equal w (-0 equals +0) and among NaNs the lower index first.  torch.topk leaves the order of equal values open; this rule is
+ * one of the orders it may produce and the one this library guarantees.
+ * Limits: 1 <= hi - lo <= 16384, 0 <= m <= hi - lo, idx_offset >= 0, idx_offset + m <= idx_stride. */
+int det6d_ext_topk_scores(int b, int n_total, int lo, int hi, int m, const float *scores, float gamma, int *idx,
+                          int idx_stride, int idx_offset, int idx_bias, det6d_stream_t stream);
+
+/* ------------------------------------------------------------------ DF-FPS -------------- */
+
+/* The weights of the reference's df-fps sampler (pointnet2_modules.py:389-414): 1 / (points of the same scene and slice in
+ * the same 2 m x 2 m pillar).  xyz (b, n_total, 3); weights (b, hi - lo), dense.  With the constants of that branch (range
+ * origin x = 0, y = -39.68, scale_y = 40), in fp32: cx = floor((x - 0.0f) / 2.0f), cy = floor((y - (-39.68f)) / 2.0f),
+ * key = cx * 40 + cy; count[k] = points of the scene's slice whose key equals key[k] (a point outside the range counts with
+ * whatever pillar its key collides with); weights[s, k] = 1.0f / (float)count[k], correctly rounded.
+ * (tests/models/pillar_density.py.)  The picks are det6d_fps_weights(xyz slice, weights, m) of det6d_ops.h.
+ * Counts are PER SCENE.  The reference adds batch_index * 1400 to the key and counts over the batch, so that a point with
+ * cx >= 35 or a negative key shares a count with a pillar of a neighbouring scene of the batch; here a scene's weights
+ * never depend on its neighbours.  The two agree for every scene whose keys lie in [0, 1400) and for batches of one scene.
+ * Input domain: finite coordinates with |x|, |y| <= 1e6; beyond it the reference's float -> long conversion of the pillar
+ * coordinate is itself undefined, and so is the result here.
+ * Limits: 1 <= hi - lo <= 16384. */
+int det6d_ext_pillar_weights(int b, int n_total, int lo, int hi, const float *xyz, float *weights, det6d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

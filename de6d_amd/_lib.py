@@ -186,6 +186,9 @@ _EXT_SIGNATURES = {
     "det6d_ext_fps_matrix": [c_int, c_int, c_int, _P, _P, _P, _P],
     "det6d_ext_topk_scores": [c_int, c_int, c_int, c_int, c_int, _P, c_float, _P, c_int, c_int, c_int, _P],
     "det6d_ext_pillar_weights": [c_int, c_int, c_int, c_int, _P, _P, _P],
+    "det6d_ext_points_in_boxes9": [c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P],
+    "det6d_ext_assign_targets9": [c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, c_int, c_float,
+                                  _P, _P, _P, c_int, c_int, _P],
 }
 #: every symbol include/det6d_ext.h declares (tests/test_ext_boundary.py checks the export table)
 EXT_EXPORTED_SYMBOLS = sorted(list(_EXT_SIGNATURES) + ["det6d_ext_version", "det6d_ext_last_error",

@@ -309,7 +309,7 @@ int det6d_ext_fail(const char *fmt, ...) {
   return DET6D_EINVAL;
 }
 
-DET6D_API const char *det6d_ext_version(void) { return "det6d-hip-ext gfx950 ext2"; }
+DET6D_API const char *det6d_ext_version(void) { return "det6d-hip-ext gfx950 ext3"; }
 DET6D_API const char *det6d_ext_last_error(void) { return g_ext_err; }
 
 DET6D_API long long det6d_ext_fps_features_workspace_bytes(int b, int n) {

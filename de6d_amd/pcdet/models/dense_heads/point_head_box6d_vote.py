@@ -6,7 +6,14 @@ inference branch, on fused HIP ops:
   around the votes (ball query + fused grouped GEMMs + max-pool) -> shared / cls / reg FCs (GEMMs)
   -> PointBinResidual6DCoder.decode (kernel).
 
-Target assignment and losses (:101-776) are training-only and out of scope.
+Target assignment (:171-326, :387-407) exists for the argument combinations Det6D's training forward uses
+(set_ignore_flag=False; ASSIGN_METHOD: mask with the ball constraint) as one HIP kernel per assignment
+(csrc/ext/box_targets.hip): assign_stack_targets_simple / assign_targets_simple (vote targets),
+assign_stack_targets_mask / assign_targets (class, box and encoded regression targets) and
+assign_training_targets(batch_dict), which labels the output of an eval forward the way the reference's training
+forward (:837-844, :872-876) would.  Nothing in it reads a result on the host: it can be captured into a graph.
+forward() in training mode, the set_ignore_flag=True variants, ASSIGN_METHOD: iou, the SASA labels, losses and
+centerness (:101-170, :328-385, :409-776) are not implemented and raise.
 Parameters live under the reference's names (vote_layers, SA_module.mlps, shared_fc_layer,
 cls_layers, reg_layers) so reference checkpoints load unchanged."""
 import torch
@@ -15,6 +22,7 @@ import torch.nn as nn
 from ...ops.pointnet2.pointnet2_batch import pointnet2_modules
 from ...ops.pointnet2.pointnet2_batch.pointnet2_modules import fold_sequential, rows_ld, round4, run_chain, to_device
 from ...ops_backend import fused
+from ....ops import box_targets
 from ...utils import box_coder_utils
 
 
@@ -50,6 +58,7 @@ class PointHeadBox6DVote(nn.Module):
         self.init_weights()
         self.forward_ret_dict = None
         self._folded = None
+        self._extra_width = None
 
     @staticmethod
     def make_fc_layers(input_channels, output_channels, fc_list):
@@ -163,3 +172,94 @@ class PointHeadBox6DVote(nn.Module):
         self.forward_ret_dict = {'batch_size': batch_size, 'point_cls_preds': point_cls_preds,
                                  'point_reg_preds': point_reg_preds, 'point_box_preds': boxes}
         return batch_dict
+
+    # ---- target assignment (point_head_box6d_vote.py:171-326, :387-407) ------------------------------------------------
+    @staticmethod
+    def _check_targets_input(points, gt_boxes):
+        assert len(points.shape) == 2 and points.shape[1] == 4, 'points.shape=%s' % str(points.shape)
+        assert len(gt_boxes.shape) == 3 and gt_boxes.shape[2] >= 9, 'gt_boxes.shape=%s' % str(gt_boxes.shape)
+        return points.contiguous(), gt_boxes.contiguous()
+
+    def _extra_width_tensor(self, extra_width, device):
+        """the 3 floats of VOTE_EXTRA_WIDTH on the device, uploaded once (an upload cannot be captured into a graph)"""
+        if extra_width is None or torch.is_tensor(extra_width):
+            return extra_width
+        key = (tuple(float(v) for v in extra_width), device)
+        if self._extra_width is None or self._extra_width[0] != key:
+            self._extra_width = (key, torch.tensor(key[0], dtype=torch.float32, device=device))
+        return self._extra_width[1]
+
+    def _assign_simple(self, points, gt_boxes, extra_width):
+        points, gt_boxes = self._check_targets_input(points, gt_boxes)
+        _, cls_labels, reg_labels = box_targets.assign_targets9(
+            points, gt_boxes, extra_width=self._extra_width_tensor(extra_width, points.device), n_cols=3)
+        return {'point_cls_labels': cls_labels, 'point_reg_labels': reg_labels}
+
+    def assign_stack_targets_simple(self, points, gt_boxes, extend_gt_boxes=None, set_ignore_flag=True):
+        """vote targets (:171-226).  points (N1 + N2 + ..., 4) [bs_idx, x, y, z], gt_boxes (B, M, 9 + 1) ->
+        point_cls_labels (N,) int64: 1 inside a box, else 0; point_reg_labels (N, 3): the centre of that box, else 0"""
+        if set_ignore_flag or extend_gt_boxes is not None:
+            raise NotImplementedError("assign_stack_targets_simple: set_ignore_flag=True / extend_gt_boxes is not used by "
+                                      "Det6D's training forward and is not implemented")
+        return self._assign_simple(points, gt_boxes, None)
+
+    def assign_targets_simple(self, points, gt_boxes, extra_width=None, set_ignore_flag=True):
+        """:228-253: assign_stack_targets_simple on the boxes enlarged by extra_width (box_utils.enlarge_box3d; the kernel adds
+        it to dx, dy, dz itself)"""
+        if set_ignore_flag:
+            raise NotImplementedError("assign_targets_simple: set_ignore_flag=True is not used by Det6D's training forward "
+                                      "and is not implemented")
+        return self._assign_simple(points, gt_boxes, extra_width)
+
+    def assign_stack_targets_mask(self, points, gt_boxes, extend_gt_boxes=None, set_ignore_flag=True,
+                                  use_ball_constraint=False, central_radius=2.0):
+        """:255-326 with set_ignore_flag=False, use_ball_constraint=True.  A point inside a box and closer than
+        central_radius to its centre is foreground; inside but not closer: label -1.  -> point_cls_labels (N,) int64,
+        point_reg_labels (N, code_size) = box_coder.encode_torch(box, point), point_box_labels (N, C - 1) = the box
+        without its class column; both zero for every point that is not foreground."""
+        assert set_ignore_flag != use_ball_constraint, 'Choose one only!'
+        if set_ignore_flag:
+            # the reference calls the yaw-only roiaware_pool3d op with 9-wide boxes here (:289): it cannot have run
+            raise NotImplementedError("assign_stack_targets_mask: set_ignore_flag=True (yaw-only roiaware_pool3d boxes) is "
+                                      "not implemented")
+        if not central_radius > 0:
+            raise ValueError("assign_stack_targets_mask: central_radius = %r must be positive" % (central_radius,))
+        points, gt_boxes = self._check_targets_input(points, gt_boxes)
+        assert gt_boxes.shape[2] >= 10, 'gt_boxes.shape=%s (the last column is the class)' % str(gt_boxes.shape)
+        ncol = gt_boxes.shape[2] - 1
+        box_idx, cls_labels, box_labels = box_targets.assign_targets9(
+            points, gt_boxes, class_col=ncol, num_class=self.num_class, central_radius=central_radius, n_cols=ncol)
+        fg = ((box_idx >= 0) & (cls_labels != -1)).unsqueeze(-1)
+        # encode EVERY row and mask: the reference's boolean indexing would read the number of foreground points on the host.
+        # encode_torch clamps the sizes of its argument in place; like the reference (:310-318) the box labels keep that clamp.
+        code = self.box_coder.encode_torch(box_labels, points[:, 1:4])[..., :self.box_coder.code_size]
+        zero = code.new_zeros(())
+        return {'point_cls_labels': cls_labels,
+                'point_reg_labels': torch.where(fg, code, zero),
+                'point_box_labels': torch.where(fg, box_labels, zero)}
+
+    def assign_targets(self, input_dict):
+        """:387-407: the targets of the vote points, by TARGET_CONFIG.ASSIGN_METHOD (only 'mask')"""
+        target_cfg = self.model_cfg.TARGET_CONFIG
+        if target_cfg.get('ASSIGN_METHOD', None) is None:
+            raise KeyError("TARGET_CONFIG.ASSIGN_METHOD is not set (the target assignment needs it: 'mask')")
+        if target_cfg.ASSIGN_METHOD != 'mask':
+            raise NotImplementedError("TARGET_CONFIG.ASSIGN_METHOD: %s is not implemented (only 'mask')" % target_cfg.ASSIGN_METHOD)
+        points = input_dict['point_vote_coords']
+        gt_boxes = input_dict['gt_boxes']
+        assert points.shape.__len__() == 2, 'points.shape=%s' % str(points.shape)
+        assert gt_boxes.shape.__len__() == 3, 'gt_boxes.shape=%s' % str(gt_boxes.shape)
+        return self.assign_stack_targets_mask(points=points, gt_boxes=gt_boxes, set_ignore_flag=False, use_ball_constraint=True,
+                                              central_radius=target_cfg.get('GT_CENTRAL_RADIUS', 2.0))
+
+    def assign_training_targets(self, batch_dict):
+        """The labels the reference's training forward puts into forward_ret_dict (:837-844, :872-876), for the batch_dict an
+        eval forward returned plus batch_dict['gt_boxes'] (B, M, 9 + 1): vote_cls_labels / vote_reg_labels of the candidate
+        points, point_cls_labels / point_reg_labels / point_box_labels of the vote points."""
+        extra_width = self.model_cfg.TARGET_CONFIG.get('VOTE_EXTRA_WIDTH', None)
+        vote = self.assign_targets_simple(points=batch_dict['point_candidate_coords'], gt_boxes=batch_dict['gt_boxes'],
+                                          extra_width=extra_width, set_ignore_flag=False)
+        point = self.assign_targets(batch_dict)
+        return {'vote_cls_labels': vote['point_cls_labels'], 'vote_reg_labels': vote['point_reg_labels'],
+                'point_cls_labels': point['point_cls_labels'], 'point_reg_labels': point['point_reg_labels'],
+                'point_box_labels': point['point_box_labels']}

@@ -50,13 +50,13 @@ class PointBinResidual6DCoder(object):
         pitch = ry
         if not self.ground_aware:
             return pitch,
-        res = torch.zeros_like(pitch)
+        # torch.where, not the reference's res[flag] = ...: the same values without the host synchronisation of boolean indexing
         if self.minus:
             flag = torch.abs(pitch) > self.ground_threshold
-            res[flag] = pitch[flag] / self.ground_factor
+            res = torch.where(flag, pitch / self.ground_factor, torch.zeros_like(pitch))
         else:
             flag = pitch < -self.ground_threshold
-            res[flag] = (-self.ground_threshold - pitch[flag]) / self.ground_factor
+            res = torch.where(flag, (-self.ground_threshold - pitch) / self.ground_factor, torch.zeros_like(pitch))
         return flag.long(), res
 
     def encode_torch(self, gt_boxes, points, gt_classes=None):

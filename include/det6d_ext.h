@@ -70,6 +70,49 @@ int det6d_ext_topk_scores(int b, int n_total, int lo, int hi, int m, const float
  * Limits: 1 <= hi - lo <= 16384. */
 int det6d_ext_pillar_weights(int b, int n_total, int lo, int hi, const float *xyz, float *weights, det6d_stream_t stream);
 
+/* ------------------------------------------------------------------ target assignment -- */
+
+/* Which full-pose box does each point lie in — the reference's box_utils.points_in_boxes3d (box_utils.py:336-350, a host-side
+ * Delaunay hull test per box) and the two label assignments PointHeadBox6DVote builds on it (point_head_box6d_vote.py:171-326
+ * with set_ignore_flag=False), as one kernel.
+ * points (n_points, ld_points): coordinates in columns xyz_col .. xyz_col + 2; the scene of row r is (int)points[r][bs_col] when
+ * bs_col >= 0 (rows of any scene in any order) and r / n_per_scene otherwise.  A row whose scene is not in [0, b) (NaN
+ * included) is background.  boxes (b, m, ld_boxes): columns 0 .. 8 are [x, y, z, dx, dy, dz, rz, ry, rx]; extra_width (3 floats
+ * or NULL = zeros) is added to dx, dy, dz (box_utils.enlarge_box3d).
+ * box_idx[r] = the HIGHEST index of a box of the row's scene that contains the point, -1 if none (the reference assigns box
+ * by box in ascending order, the last assignment stays).
+ * Arithmetic (exact, tests/models/box_targets.py; every fp32 operation rounded once, nothing contracted):
+ *   per box: (s*, c*) = d6_sincosf of rz, ry, rx (det6d_math.h); R = Rx(rx) Ry(ry) Rz(rz) (scipy's 'zyx' of
+ *   box_utils.py:57-71), with t = sx*sy and u = cx*sy:
+ *     R00 = cy*cz           R01 = -(cy*sz)        R02 = sy
+ *     R10 = cx*sz + t*cz    R11 = cx*cz - t*sz    R12 = -(sx*cy)
+ *     R20 = sx*sz - u*cz    R21 = sx*cz + u*sz    R22 = cx*cy
+ *   w_k = d_k + extra_k; half_k = 0.5f * w_k; the box takes part only if w_x > 0 and w_y > 0 and w_z > 0 (NaN fails: the
+ *   all-zero rows that pad gt_boxes contain nothing, as in the reference);
+ *   per pair: d = p - c (fp32), l_k = fmaf(d_z, R2k, fmaf(d_y, R1k, d_x * R0k)); inside iff fabsf(l_k) <= half_k for
+ *   k = x, y, z (a NaN anywhere: outside).  Of the boxes that contain the point the one with the highest index is taken.
+ * Limits: 0 <= n_points <= 2^24, 0 <= b <= 4096, 0 <= m <= 1024, 3 <= ld_points <= 1024, 0 <= xyz_col <= ld_points - 3,
+ * bs_col < ld_points, n_per_scene >= 1 when bs_col < 0, 9 <= ld_boxes <= 1024.  With n_points == 0, b == 0 or m == 0 nothing is
+ * launched and nothing is written (no box: the caller's outputs keep their fill, -1 / 0). */
+int det6d_ext_points_in_boxes9(int n_points, const float *points, int ld_points, int xyz_col, int bs_col, int n_per_scene,
+                               int b, int m, const float *boxes, int ld_boxes, const float *extra_width, int *box_idx,
+                               det6d_stream_t stream);
+
+/* det6d_ext_points_in_boxes9 plus the labels of the head, in the same launch.  For a point inside a box, with d = p - c of the
+ * winning box (the fp32 differences above): near = central_radius <= 0 (no ball constraint), or else, in double, each operation
+ * rounded once, ((double)d_x*d_x + (double)d_y*d_y) + (double)d_z*d_z < (double)central_radius * (double)central_radius.
+ *   cls_labels[r] = 0 outside every box; -1 inside but not near (ignored); otherwise 1 if num_class == 1 or class_col < 0,
+ *                   else (long long)box[class_col];
+ *   box_labels[r][0 .. n_cols) = columns 0 .. n_cols of the winning box if inside and near, zeros otherwise (columns from
+ *                   n_cols to ld_box_labels are left alone).  n_cols = 3: the vote targets; n_cols = 9: point_box_labels.
+ * Any of box_idx, cls_labels, box_labels may be NULL (not all three).
+ * Further limits: class_col < ld_boxes, num_class >= 1, central_radius not NaN, 0 <= n_cols <= ld_boxes,
+ * n_cols <= ld_box_labels <= 1024. */
+int det6d_ext_assign_targets9(int n_points, const float *points, int ld_points, int xyz_col, int bs_col, int n_per_scene,
+                              int b, int m, const float *boxes, int ld_boxes, const float *extra_width, int class_col,
+                              int num_class, float central_radius, int *box_idx, long long *cls_labels, float *box_labels,
+                              int ld_box_labels, int n_cols, det6d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

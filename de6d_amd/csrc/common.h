@@ -62,8 +62,6 @@ static inline bool det6d_env_set(const char *) { return false; }
 #endif
 #ifdef DET6D_EXPERIMENTS
 #define D6_DBG_IS(v) (dbg == (v))
-// DET6D_DBG_POISON_LDS=<pattern>: fill the LDS of every CU before a sampler kernel (fps_seq.hip; tests only)
-void det6d_dbg_poison_lds_hook(hipStream_t stream);
 // DET6D_GEMM_PRIO=1 (experiments build): every wave of the GEMM family raises its issue priority (s_setprio 3) — does the matrix
 // stream lose issue slots to the vector instructions of the kernels beside it?  (scripts/r05/gpu_t34.sh)
 #define D6_GEMM_PRIO_DECL __device__ int d6_gemm_prio_flag = 0;

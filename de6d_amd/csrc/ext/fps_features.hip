@@ -7,7 +7,7 @@
 //    |xyz|^2 and min-distance in registers (k = h + j * S, S = opt_n_threads(n), j = 0 .. PPT-1); |f|^2 is computed once
 //    into the workspace and read beside the feature row of a point that needs it (in registers it spills at PPT = 16);
 //  * the per-thread arg-max is the reference's strict > scan; the cross-thread / cross-wave rule is its halving tree,
-//    restated as the order key of fps_multi.h (sq_tie_key): max value, then smallest (bitrev(k mod S), k);
+//    restated as the order key of fps_common.h (fps_tie_key): max value, then smallest (bitrev(k mod S), k);
 //  * every wave loads its candidate's row into LDS before the one barrier of the round (xyz as is, features x -2), so
 //    the round after the decision starts without a dependent global load;
 //  * exact skip: both parts of d are >= 0 and fl(a + b) >= a for b >= 0, so d >= d_xyz in floating point.  A point whose
@@ -16,24 +16,12 @@
 // The matrix form (ffps_matrix_kernel) runs the same selection core on a caller-supplied matrix: it pins that core against
 // the reference's own matrices (tests/golden/ffps_ref.npz).
 #include "../common.h"
-#include "../fps_multi.h"
+#include "../fps_common.h"
 #include "../../../include/det6d_ext.h"
 #include "ext_common.h"
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 namespace {
-
-thread_local char g_ext_err[256] = "";
-
-int ext_fail(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_ext_err, sizeof(g_ext_err), fmt, ap);
-  va_end(ap);
-  return DET6D_EINVAL;
-}
 
 constexpr int kFfMaxC = 256;
 constexpr int kFfMaxWaves = 16;
@@ -53,9 +41,6 @@ struct FfPayload {
   float nxyz, nf, pad[2];
 };
 
-// sq_tie_key of fps_multi.h, on int keys of this file
-__device__ __forceinline__ unsigned ff_key(int k, int log2s) { return sq_tie_key(k, log2s); }
-
 // reference's clamp_min(0) of a Gram entry: NaN stays NaN (the fminf of the round then ignores the point's distance)
 __device__ __forceinline__ float ff_clamp0(float g) { return g <= 0.f ? 0.f : g; }
 
@@ -69,11 +54,11 @@ __device__ __forceinline__ int ff_decide(float best, int bk, bool live, int log2
   const float wm = d6_wave_max(v);
   const u64 tie = __ballot(v == wm);
   int wl = __builtin_ctzll(tie);
-  if (__popcll(tie) != 1) wl = sq_min_key_lane(tie, ff_key(bk, log2s));
+  if (__popcll(tie) != 1) wl = fps_min_key_lane(tie, fps_tie_key(bk, log2s));
   const int wk = d6_readlane_i(bk, wl);
   if (lane == 0) {
     sl[wave].val = wm;
-    sl[wave].key = ff_key(wk, log2s);
+    sl[wave].key = fps_tie_key(wk, log2s);
     sl[wave].k = wk;
   }
   payload(wk);
@@ -83,7 +68,7 @@ __device__ __forceinline__ int ff_decide(float best, int bk, bool live, int log2
   const float bm = d6_wave_max(v2);
   const u64 tie2 = __ballot(in && v2 == bm);
   int ww = __builtin_ctzll(tie2);
-  if (__popcll(tie2) != 1) ww = sq_min_key_lane(tie2, in ? sl[lane].key : 0xFFFFFFFFu);
+  if (__popcll(tie2) != 1) ww = fps_min_key_lane(tie2, in ? sl[lane].key : 0xFFFFFFFFu);
   return ww;
 }
 
@@ -285,32 +270,9 @@ __global__ __launch_bounds__(1024) void ffps_matrix_kernel(int n, int m, int log
   }
 }
 
-// cuda_utils.h:10-14 opt_n_threads, as a power of two
-int ff_opt_n_threads_log2(int work_size) {
-  int pow_2 = (int)(log((double)work_size) / log(2.0));
-  if (pow_2 > 10) pow_2 = 10;
-  if (pow_2 < 0) pow_2 = 0;
-  return pow_2;
-}
-
 long long ff_stats_offset(int b, int n) { return ((long long)b * n * 8 + 15) / 16 * 16; }
 
 }  // namespace
-
-void det6d_set_error(const char *what, hipError_t err) {
-  snprintf(g_ext_err, sizeof(g_ext_err), "%s: %s", what, hipGetErrorString(err));
-}
-
-int det6d_ext_fail(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_ext_err, sizeof(g_ext_err), fmt, ap);
-  va_end(ap);
-  return DET6D_EINVAL;
-}
-
-DET6D_API const char *det6d_ext_version(void) { return "det6d-hip-ext gfx950 ext3"; }
-DET6D_API const char *det6d_ext_last_error(void) { return g_ext_err; }
 
 DET6D_API long long det6d_ext_fps_features_workspace_bytes(int b, int n) {
   if (b <= 0 || n <= 0) return 0;
@@ -320,23 +282,23 @@ DET6D_API long long det6d_ext_fps_features_workspace_bytes(int b, int n) {
 DET6D_API int det6d_ext_fps_features(int b, int n_total, int lo, int hi, int m, const float *rows, int ld, int c, float gamma,
                                      void *workspace, long long ws_bytes, int *idx, int idx_stride, int idx_offset, int idx_bias,
                                      det6d_stream_t stream) {
-  if (b < 0) return ext_fail("det6d_ext_fps_features: b = %d < 0", b);
+  if (b < 0) return det6d_ext_fail("det6d_ext_fps_features: b = %d < 0", b);
   if (n_total <= 0 || lo < 0 || hi > n_total || hi <= lo)
-    return ext_fail("det6d_ext_fps_features: bad slice [%d, %d) of %d points", lo, hi, n_total);
+    return det6d_ext_fail("det6d_ext_fps_features: bad slice [%d, %d) of %d points", lo, hi, n_total);
   const int n = hi - lo;
-  if (n > kFfMaxN) return ext_fail("det6d_ext_fps_features: %d points per scene (at most %d)", n, kFfMaxN);
-  if (c < 0 || c > kFfMaxC) return ext_fail("det6d_ext_fps_features: %d feature channels (0 .. %d)", c, kFfMaxC);
-  if (ld < c + 3 || ld % 4 != 0) return ext_fail("det6d_ext_fps_features: row stride %d (needs >= c + 3 = %d, multiple of 4)", ld, c + 3);
+  if (n > kFfMaxN) return det6d_ext_fail("det6d_ext_fps_features: %d points per scene (at most %d)", n, kFfMaxN);
+  if (c < 0 || c > kFfMaxC) return det6d_ext_fail("det6d_ext_fps_features: %d feature channels (0 .. %d)", c, kFfMaxC);
+  if (ld < c + 3 || ld % 4 != 0) return det6d_ext_fail("det6d_ext_fps_features: row stride %d (needs >= c + 3 = %d, multiple of 4)", ld, c + 3);
   if (m < 0 || idx_offset < 0 || idx_stride < idx_offset + m)
-    return ext_fail("det6d_ext_fps_features: m = %d at offset %d does not fit an index row of %d", m, idx_offset, idx_stride);
+    return det6d_ext_fail("det6d_ext_fps_features: m = %d at offset %d does not fit an index row of %d", m, idx_offset, idx_stride);
   if (b == 0 || m == 0) return DET6D_OK;
-  if (!rows || !idx || !workspace) return ext_fail("det6d_ext_fps_features: null pointer");
-  if (((uintptr_t)rows & 15u) != 0) return ext_fail("det6d_ext_fps_features: rows must be 16-byte aligned");
-  if (((uintptr_t)workspace & 15u) != 0) return ext_fail("det6d_ext_fps_features: workspace must be 16-byte aligned");
+  if (!rows || !idx || !workspace) return det6d_ext_fail("det6d_ext_fps_features: null pointer");
+  if (((uintptr_t)rows & 15u) != 0) return det6d_ext_fail("det6d_ext_fps_features: rows must be 16-byte aligned");
+  if (((uintptr_t)workspace & 15u) != 0) return det6d_ext_fail("det6d_ext_fps_features: workspace must be 16-byte aligned");
   if (ws_bytes < det6d_ext_fps_features_workspace_bytes(b, n))
-    return ext_fail("det6d_ext_fps_features: workspace of %lld bytes (needs %lld)", ws_bytes,
+    return det6d_ext_fail("det6d_ext_fps_features: workspace of %lld bytes (needs %lld)", ws_bytes,
                     det6d_ext_fps_features_workspace_bytes(b, n));
-  const int log2s = ff_opt_n_threads_log2(n);
+  const int log2s = fps_opt_n_threads_log2(n);
   const int S = 1 << log2s;
   const int ppt = (n + S - 1) / S;
   const dim3 grid(b), block(S < 64 ? 64 : S);
@@ -358,11 +320,11 @@ DET6D_API int det6d_ext_fps_features(int b, int n_total, int lo, int hi, int m, 
 }
 
 DET6D_API int det6d_ext_fps_matrix(int b, int n, int m, const float *matrix, float *temp, int *idx, det6d_stream_t stream) {
-  if (b < 0 || m < 0) return ext_fail("det6d_ext_fps_matrix: b = %d, m = %d", b, m);
-  if (n <= 0 || n > kFfMaxN) return ext_fail("det6d_ext_fps_matrix: %d points per scene (1 .. %d)", n, kFfMaxN);
+  if (b < 0 || m < 0) return det6d_ext_fail("det6d_ext_fps_matrix: b = %d, m = %d", b, m);
+  if (n <= 0 || n > kFfMaxN) return det6d_ext_fail("det6d_ext_fps_matrix: %d points per scene (1 .. %d)", n, kFfMaxN);
   if (b == 0 || m == 0) return DET6D_OK;
-  if (!matrix || !temp || !idx) return ext_fail("det6d_ext_fps_matrix: null pointer");
-  const int log2s = ff_opt_n_threads_log2(n);
+  if (!matrix || !temp || !idx) return det6d_ext_fail("det6d_ext_fps_matrix: null pointer");
+  const int log2s = fps_opt_n_threads_log2(n);
   const int S = 1 << log2s;
   const int ppt = (n + S - 1) / S;
   const dim3 grid(b), block(S < 64 ? 64 : S);

@@ -15,16 +15,12 @@
 //  * the winner's coordinates travel with the (value, index) pair through LDS, so the next round
 //    starts without a dependent global load;
 //  * LDS slots are double-buffered by round parity: one s_barrier per round.
-#include "common.h"
+#include "fps_common.h"
 #include <stdlib.h>
 
 namespace {
 
 constexpr int kMaxPPT = 16;
-
-__device__ __forceinline__ unsigned bitrev_n(unsigned v, int bits) {
-  return bits == 0 ? 0u : (__builtin_bitreverse32(v) >> (32 - bits));
-}
 
 // Strided batch view + fused pre/post steps (used by det6d_fps_fused; the reference-shaped entry
 // points pass the dense defaults): per-scene strides in elements, an index offset added on output
@@ -61,7 +57,7 @@ __global__ __launch_bounds__(1024) void fps_reg_kernel(int n, int m, int log2s,
   const int wave = h >> 6;
   const int nwaves = (blockDim.x + 63) >> 6;
   const bool live = h < S;
-  const int v = (int)bitrev_n((unsigned)h, log2s);
+  const int v = (int)fps_bitrev((unsigned)h, log2s);
 
   xyz += (size_t)blockIdx.x * vw.xyz_bstride;
   if (temp) temp += (size_t)blockIdx.x * vw.temp_bstride;
@@ -171,24 +167,6 @@ __global__ __launch_bounds__(1024) void fps_reg_kernel(int n, int m, int log2s,
   }
 }
 
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// coordinates of slot `ws` (wave-uniform) of lane `wl`: scalar branches down to one slot
-template <int LO, int HI, int N>
-__device__ __forceinline__ void pick_slot(int ws, int wl, const float (&px)[N], const float (&py)[N],
-                                          const float (&pz)[N], float &sx, float &sy, float &sz) {
-  if constexpr (HI - LO == 1) {
-    sx = d6_readlane_f(px[LO], wl);
-    sy = d6_readlane_f(py[LO], wl);
-    sz = d6_readlane_f(pz[LO], wl);
-  } else {
-    constexpr int MID = (LO + HI) / 2;
-    if (ws < MID) pick_slot<LO, MID>(ws, wl, px, py, pz, sx, sy, sz);
-    else pick_slot<MID, HI>(ws, wl, px, py, pz, sx, sy, sz);
-  }
-}
-
 // Fat-thread fast path.  The reference's block has S = opt_n_threads(N) virtual threads; their
 // tie priority is p = bitrev(v).  Here T = 2^LOG2T <= S hardware threads each emulate S/T virtual
 // threads with CONSECUTIVE priorities p = h*S/T .. (h+1)*S/T - 1 and scan their SLOTS = N/T points in
@@ -236,7 +214,7 @@ __global__ __launch_bounds__(1 << LOG2T) void fps_fat_kernel(int n, int m, int l
 
   auto slot_point = [&](int s) {  // slot -> point index k = v + S * j
     const int pl = s >> log2pptv, j = s & ((1 << log2pptv) - 1);
-    const int v = (int)bitrev_n((unsigned)((h << log2vpt) + pl), log2s);
+    const int v = (int)fps_bitrev((unsigned)((h << log2vpt) + pl), log2s);
     return v + (j << log2s);
   };
 
@@ -286,13 +264,13 @@ __global__ __launch_bounds__(1 << LOG2T) void fps_fat_kernel(int n, int m, int l
         best = up ? pwf[s] : best;
       }
     } else {
-      const f32x2 c2x = {cx, cx}, c2y = {cy, cy}, c2z = {cz, cz};
+      const fps_f32x2 c2x = {cx, cx}, c2y = {cy, cy}, c2z = {cz, cz};
 #pragma unroll
       for (int q = 0; q < H; ++q) {
-        const f32x2 dx = f32x2{px[2 * q], px[2 * q + 1]} - c2x;
-        const f32x2 dy = f32x2{py[2 * q], py[2 * q + 1]} - c2y;
-        const f32x2 dz = f32x2{pz[2 * q], pz[2 * q + 1]} - c2z;
-        f32x2 d = dy * dy;
+        const fps_f32x2 dx = fps_f32x2{px[2 * q], px[2 * q + 1]} - c2x;
+        const fps_f32x2 dy = fps_f32x2{py[2 * q], py[2 * q + 1]} - c2y;
+        const fps_f32x2 dz = fps_f32x2{pz[2 * q], pz[2 * q + 1]} - c2z;
+        fps_f32x2 d = dy * dy;
         d = __builtin_elementwise_fma(dx, dx, d);
         d = __builtin_elementwise_fma(dz, dz, d);
 #pragma unroll
@@ -320,7 +298,7 @@ __global__ __launch_bounds__(1 << LOG2T) void fps_fat_kernel(int n, int m, int l
     if (ws >= 0) {
       old = d6_readlane_i(slot_point(ws), wl);
       // ws is wave-uniform: a scalar binary search over the slots, then three v_readlane
-      pick_slot<0, SLOTS>(ws, wl, px, py, pz, sx, sy, sz);
+      fps_pick_slot<0, SLOTS>(ws, wl, px, py, pz, sx, sy, sz);
     } else {
       old = 0;
       sx = xyz[0]; sy = xyz[1]; sz = xyz[2];
@@ -374,7 +352,7 @@ __global__ __launch_bounds__(1024) void fps_mem_kernel(int n, int m, int log2s,
   const int wave = h >> 6;
   const int nwaves = (blockDim.x + 63) >> 6;
   const bool live = h < S;
-  const int v = (int)bitrev_n((unsigned)h, log2s);
+  const int v = (int)fps_bitrev((unsigned)h, log2s);
   xyz += (size_t)blockIdx.x * vw.xyz_bstride;
   if (temp) temp += (size_t)blockIdx.x * vw.temp_bstride;
   idxs += (size_t)blockIdx.x * vw.idx_bstride;
@@ -428,14 +406,6 @@ __global__ __launch_bounds__(1024) void fps_mem_kernel(int n, int m, int log2s,
   }
 }
 
-// core/pcdet/ops/pointnet2/pointnet2_batch/src/cuda_utils.h:10-14 (same double formula, same libm)
-int opt_n_threads_log2(int work_size) {
-  int pow_2 = (int)(log((double)work_size) / log(2.0));
-  if (pow_2 > 10) pow_2 = 10;
-  if (pow_2 < 0) pow_2 = 0;
-  return pow_2;
-}
-
 // experiments build: DET6D_FPS_NO_FASTW=1 keeps the exact-double S-FPS launch only (A/B)
 static bool no_fastw() {
   static const bool off = det6d_env_int("DET6D_FPS_NO_FASTW", 0) != 0;
@@ -448,7 +418,7 @@ int launch_fps(int b, int n, int m, const float *xyz, const float *weights, floa
   if (b < 0 || n <= 0 || m < 0) return DET6D_EINVAL;
   if (b == 0 || m == 0) return DET6D_OK;   // nothing to do (empty tensors may carry null pointers)
   if (!xyz || !idx || (W && !weights) || (!temp && !vw.init_temp)) return DET6D_EINVAL;
-  const int log2s = opt_n_threads_log2(n);
+  const int log2s = fps_opt_n_threads_log2(n);
   const int S = 1 << log2s;
   const int threads = S < 64 ? 64 : S;
   const int ppt = (n + S - 1) / S;
@@ -532,10 +502,6 @@ DET6D_API int det6d_fps_weights(int b, int n, int m, const float *xyz, const flo
   return launch_fps<true>(b, n, m, xyz, weights, temp, idx, dense_view(n, m), (hipStream_t)stream);
 }
 
-// fps_cells.hip: exact spatially pruned D-FPS of 16384-point scenes (k-d regions + bounding-box skip test)
-int det6d_fps_cells_launch(int b, int n, int m, int log2s, long long xyz_bstride, long long idx_bstride, int idx_add,
-                           const float *xyz, int *perm, int *idx, hipStream_t stream);
-
 #ifdef DET6D_EXPERIMENTS
 // ---- profiling stand-ins (DET6D_FPS_STANDIN=1|2, never a result path; scripts/experiments/gpu_whatif.py): only in
 // ---- libraries built with -DDET6D_EXPERIMENTS, never in the shipped one
@@ -568,32 +534,28 @@ __global__ __launch_bounds__(512) void fps_standin_kernel(int n, int m, int *idx
 }  // namespace
 #endif
 
-// fps_coop.hip: register-resident D-FPS of 32768 / 65536-point scenes by cooperating workgroups
-bool det6d_fps_coop_handles(int n);
-long long det6d_fps_coop_workspace_bytes(int b, int n);
-int det6d_fps_cells_w_launch(int b, int n, int m, int log2s, long long xyz_bstride, long long idx_bstride, int idx_add,
-                             const float *xyz, int *perm, int *idx, const float *weights, long long w_bstride, float gamma,
-                             int w_is_score, hipStream_t stream);      // fps_cells.hip
-bool det6d_fps_coop_fits_device(int n);      // fps_coop.hip: the current device holds one cooperative launch (>= 8 x parts CUs)
-int det6d_fps_coop_launch(int b, int n, int m, int log2s, long long xyz_bstride, long long idx_bstride, int idx_add,
-                          const float *xyz, void *workspace, int *idx, hipStream_t stream);
-
-int det6d_fps_coop_status(int b, int n, const void *workspace, hipStream_t stream);
-long long det6d_fps_coop_status_offset(int b, int n);
-
-DET6D_API int det6d_fps_fused_status(int b, int n, const float *temp, long long temp_bytes, det6d_stream_t stream) {
-  if (!temp || !det6d_fps_coop_handles(n)) return DET6D_OK;     // only the cooperative sampler can fail after its launch
+// The cooperative sampler's workspace inside `temp` (fps_coop.hip; det6d_fps_fused_workspace_bytes leaves room for it): `temp`
+// aligned up to 256 bytes.  Null when there is no `temp`, when the cooperative sampler does not take (b, n), or when what
+// temp_bytes leaves behind the alignment is less than that sampler needs.  (Not const: the launch writes it, the status
+// queries only read it.)
+static char *coop_workspace_in(const float *temp, long long temp_bytes, int b, int n) {
+  if (!temp || !det6d_fps_coop_handles(n)) return nullptr;
+  const char *base = reinterpret_cast<const char *>(temp);
   const char *ws = reinterpret_cast<const char *>(((uintptr_t)temp + 255) & ~(uintptr_t)255);
   const long long need = det6d_fps_coop_workspace_bytes(b, n);
-  if (need <= 0 || temp_bytes - (ws - reinterpret_cast<const char *>(temp)) < need) return DET6D_OK;
+  if (need <= 0 || temp_bytes - (ws - base) < need) return nullptr;
+  return const_cast<char *>(ws);
+}
+
+DET6D_API int det6d_fps_fused_status(int b, int n, const float *temp, long long temp_bytes, det6d_stream_t stream) {
+  const char *ws = coop_workspace_in(temp, temp_bytes, b, n);
+  if (!ws) return DET6D_OK;     // only the cooperative sampler can fail after its launch
   return det6d_fps_coop_status(b, n, ws, (hipStream_t)stream);
 }
 
 DET6D_API long long det6d_fps_fused_status_offset(int b, int n, const float *temp, long long temp_bytes) {
-  if (!temp || !det6d_fps_coop_handles(n)) return -1;
-  const char *ws = reinterpret_cast<const char *>(((uintptr_t)temp + 255) & ~(uintptr_t)255);
-  const long long need = det6d_fps_coop_workspace_bytes(b, n);
-  if (need <= 0 || temp_bytes - (ws - reinterpret_cast<const char *>(temp)) < need) return -1;
+  const char *ws = coop_workspace_in(temp, temp_bytes, b, n);
+  if (!ws) return -1;
   return (ws - reinterpret_cast<const char *>(temp)) + det6d_fps_coop_status_offset(b, n);
 }
 
@@ -627,7 +589,7 @@ DET6D_API int det6d_fps_fused(int b, int n_total, int lo, int hi, int m, const f
   // (knobs / experiments build): the one-pick fat-thread kernel of rounds 2-5
   static const int seqw = det6d_env_int("DET6D_FPS_SEQW", 1);
   if (scores && seqw && temp && x && out && b > 0 && m > 0 && m <= n && (n == 16384 || n == 4096) && !no_fastw()) {
-    const int log2s = opt_n_threads_log2(n);
+    const int log2s = fps_opt_n_threads_log2(n);
     const int rc = det6d_fps_cells_w_launch(b, n, m, log2s, vw.xyz_bstride, vw.idx_bstride, lo + idx_bias, x, reinterpret_cast<int *>(temp),
                                             out, scores + lo, vw.w_bstride, gamma, 1, (hipStream_t)stream);
     if (rc != DET6D_OK) return rc;
@@ -648,18 +610,16 @@ DET6D_API int det6d_fps_fused(int b, int n_total, int lo, int hi, int m, const f
   // 32768 / 65536 points: the scene is held in registers by 2 / 4 cooperating workgroups (fps_coop.hip) when the caller
   // supplied the workspace det6d_fps_fused_workspace_bytes asks for; otherwise the memory-resident kernel below, 100x
   // slower, same picks
-  if (temp && x && out && b > 0 && m > 0 && det6d_fps_coop_handles(n) && det6d_fps_coop_fits_device(n)) {
-    char *ws = reinterpret_cast<char *>(((uintptr_t)temp + 255) & ~(uintptr_t)255);
-    const long long avail = temp_bytes - (ws - reinterpret_cast<char *>(temp));
-    const long long need = det6d_fps_coop_workspace_bytes(b, n);
-    if (need > 0 && avail >= need)
-      return det6d_fps_coop_launch(b, n, m, opt_n_threads_log2(n), vw.xyz_bstride, vw.idx_bstride, lo + idx_bias, x, ws, out, (hipStream_t)stream);
+  if (x && out && b > 0 && m > 0) {
+    char *ws = coop_workspace_in(temp, temp_bytes, b, n);
+    if (ws && det6d_fps_coop_fits_device(n))
+      return det6d_fps_coop_launch(b, n, m, fps_opt_n_threads_log2(n), vw.xyz_bstride, vw.idx_bstride, lo + idx_bias, x, ws, out, (hipStream_t)stream);
   }
   // 16384 / 4096 points: the multi-pick sampler of fps_seq.hip on the k-d regions of fps_cells.hip (16 / 4 points per lane in
   // registers, one bounding box per wave; the permutation lives in `temp`, which is free because the min-distances start at
   // 1e10 implicitly): same picks bit for bit, 0.51 vs 1.35 us per pick of the plain fat-thread kernel at 16384 points
   if (temp && x && out && b > 0 && m > 0 && (n == 16384 || n == 4096))
-    return det6d_fps_cells_launch(b, n, m, opt_n_threads_log2(n), vw.xyz_bstride, vw.idx_bstride, lo + idx_bias, x,
+    return det6d_fps_cells_launch(b, n, m, fps_opt_n_threads_log2(n), vw.xyz_bstride, vw.idx_bstride, lo + idx_bias, x,
                                   reinterpret_cast<int *>(temp), out, (hipStream_t)stream);
   return launch_fps<false>(b, n, m, x, nullptr, temp, out, vw, (hipStream_t)stream);
 }

@@ -18,51 +18,10 @@
 // wave-skip kernel below (one pick per round: rescan -> LDS slot -> barrier -> block arg-max) is compiled into the experiments
 // build only (DET6D_FPS_SEQ=0): same-library A/B in the pipeline, round 4: 12.40-12.43 k scenes/s against 12.86-12.95 k
 // (benchmark scenes), 5.63 against 5.73 k (ray-cast); one frame on an idle chip 4.7 against 3.7 ms.
-#include "common.h"
+#include "fps_common.h"
 #include <stdlib.h>
 
 namespace {
-
-// exclusive prefix sum over the 1024 threads of a workgroup: wave scan (six shuffles), the sixteen wave totals through LDS
-// (`wtot`: 16 words; free again when the call returns).  (Rounds 2-4 used hipcub::BlockScan here.)
-__device__ __forceinline__ unsigned block_exclusive_sum_1024(unsigned v, unsigned *__restrict__ wtot) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned o = (unsigned)__shfl_up((int)incl, off);
-    if (lane >= off) incl += o;
-  }
-  if (lane == 63) wtot[wave] = incl;
-  __syncthreads();
-  unsigned base = 0u;
-  for (int w = 0; w < wave; ++w) base += wtot[w];
-  __syncthreads();
-  return base + incl - v;
-}
-
-__device__ __forceinline__ unsigned bitrev_bits(unsigned v, int bits) {
-  return bits == 0 ? 0u : (__builtin_bitreverse32(v) >> (32 - bits));
-}
-
-// order key of point k under the reference's tie rule: smaller key wins
-__device__ __forceinline__ unsigned tie_key(int k, int log2s) {
-  return (bitrev_bits((unsigned)k & ((1u << log2s) - 1u), log2s) << (32 - log2s)) | ((unsigned)k >> log2s);
-}
-
-// lane holding the smallest key among the lanes of `cand` (slow path, ties only)
-__device__ __forceinline__ int min_key_lane(unsigned long long cand, int k, int log2s) {
-  const int lane = threadIdx.x & 63;
-  const bool mine = (cand >> lane) & 1ull;
-  unsigned key = mine ? tie_key(k, log2s) : 0xFFFFFFFFu;
-  unsigned m = key;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const unsigned o = (unsigned)__shfl_xor((int)m, off);
-    m = o < m ? o : m;
-  }
-  return __builtin_ctzll(__ballot(mine && key == m));
-}
 
 // ------------------------------------------------------------------------------------------------
 // Pre-pass: spatial order of a scene.  perm[b, p] = original index of the point at sorted position p.
@@ -129,7 +88,7 @@ __global__ __launch_bounds__(1024) void cell_sort_kernel(int n, int log2s, long 
   }
   __syncthreads();
   {
-    const unsigned off = block_exclusive_sum_1024(bins[tid], scan_tmp);     // (returns behind a barrier: every bins[tid] read)
+    const unsigned off = fps_block_exclusive_sum_1024(bins[tid], scan_tmp);     // (returns behind a barrier: every bins[tid] read)
     bins[tid] = off;
   }
   __syncthreads();
@@ -152,7 +111,7 @@ __global__ __launch_bounds__(1024) void cell_sort_kernel(int n, int log2s, long 
     unsigned cnt[QB], total = 0u, base;
 #pragma unroll
     for (int i = 0; i < QB; ++i) { cnt[i] = bins[tid * QB + i]; total += cnt[i]; }
-    base = block_exclusive_sum_1024(total, scan_tmp);
+    base = fps_block_exclusive_sum_1024(total, scan_tmp);
 #pragma unroll
     for (int i = 0; i < QB; ++i) { bins[tid * QB + i] = base; base += cnt[i]; }   // (every thread rewrites only its own bins)
   }
@@ -168,7 +127,7 @@ __global__ __launch_bounds__(1024) void cell_sort_kernel(int n, int log2s, long 
   for (int i = 0; i < IPT; ++i) {
     val[i] = sorted[tid * IPT + i];
     if (src) val[i] = src[val[i]];             // position inside the part -> point of the scene
-    key[i] = tie_key(val[i], log2s);
+    key[i] = fps_tie_key(val[i], log2s);
   }
 #pragma unroll
   for (int i = 1; i < IPT; ++i) {
@@ -197,22 +156,6 @@ __global__ __launch_bounds__(1024) void cell_sort_kernel(int n, int log2s, long 
 // reference's tie key, so the strict `>` of the scan keeps the right one inside a lane; ties between
 // lanes / waves take the explicit min-key slow path.
 // ------------------------------------------------------------------------------------------------
-template <int LO, int HI, int N>
-__device__ __forceinline__ void skip_pick(int ws, int wl, const float (&px)[N], const float (&py)[N],
-                                          const float (&pz)[N], float &sx, float &sy, float &sz) {
-  if constexpr (HI - LO == 1) {
-    sx = d6_readlane_f(px[LO], wl);
-    sy = d6_readlane_f(py[LO], wl);
-    sz = d6_readlane_f(pz[LO], wl);
-  } else {
-    constexpr int MID = (LO + HI) / 2;
-    if (ws < MID) skip_pick<LO, MID>(ws, wl, px, py, pz, sx, sy, sz);
-    else skip_pick<MID, HI>(ws, wl, px, py, pz, sx, sy, sz);
-  }
-}
-
-typedef float f32x2s __attribute__((ext_vector_type(2)));
-
 // G groups per wave: group g of a wave = slots g*SG .. (g+1)*SG-1 of its 64 lanes = 64*SG consecutive sorted
 // points with their own bounding box and cached arg-max (G = 1: one box per wave).
 // timing experiments only (DET6D_FPS_DBG=7): wall clock (100 MHz) at the first and after the last round of every scene
@@ -283,14 +226,14 @@ __global__ __launch_bounds__(64 * NW) void fps_skip_kernel(int n, int m, int log
       if (!(lb >= cg_val[g]) && !(D6_DBG_IS(3) && r > 1)) {   // wave-uniform branch (dbg 3: fixed per-round cost only)
         float best = -1.0f;
         int bs = 0;
-        const f32x2s c2x = {cx, cx}, c2y = {cy, cy}, c2z = {cz, cz};
+        const fps_f32x2 c2x = {cx, cx}, c2y = {cy, cy}, c2z = {cz, cz};
 #pragma unroll
         for (int q = 0; q < HG; ++q) {
           const int s0 = g * SG + 2 * q;
-          const f32x2s dx = f32x2s{px[s0], px[s0 + 1]} - c2x;
-          const f32x2s dy = f32x2s{py[s0], py[s0 + 1]} - c2y;
-          const f32x2s dz = f32x2s{pz[s0], pz[s0 + 1]} - c2z;
-          f32x2s d = dy * dy;
+          const fps_f32x2 dx = fps_f32x2{px[s0], px[s0 + 1]} - c2x;
+          const fps_f32x2 dy = fps_f32x2{py[s0], py[s0 + 1]} - c2y;
+          const fps_f32x2 dz = fps_f32x2{pz[s0], pz[s0 + 1]} - c2z;
+          fps_f32x2 d = dy * dy;
           d = __builtin_elementwise_fma(dx, dx, d);
           d = __builtin_elementwise_fma(dz, dz, d);
 #pragma unroll
@@ -307,15 +250,15 @@ __global__ __launch_bounds__(64 * NW) void fps_skip_kernel(int n, int m, int log
         const unsigned long long tie = __ballot(best == wmax);
         int wl = __builtin_ctzll(tie);
         const int gbase = (wave * G + g) * 64;
-        if (__popcll(tie) != 1) wl = min_key_lane(tie, (int)korig[(gbase + lane) * SG + bs], log2s);
+        if (__popcll(tie) != 1) wl = fps_min_key_lane(tie, (int)korig[(gbase + lane) * SG + bs], log2s);
         const int ws = d6_readlane_i(bs, wl);
         cg_val[g] = wmax;
         cg_k[g] = (int)korig[(gbase + wl) * SG + ws];
         float sx, sy, sz;
-        if (g == 0) skip_pick<0, SG>(ws, wl, px, py, pz, sx, sy, sz);
-        if (G > 1 && g == 1) skip_pick<(G > 1 ? SG : 0), (G > 1 ? 2 * SG : SG)>(ws + SG, wl, px, py, pz, sx, sy, sz);
-        if (G > 2 && g == 2) skip_pick<(G > 2 ? 2 * SG : 0), (G > 2 ? 3 * SG : SG)>(ws + 2 * SG, wl, px, py, pz, sx, sy, sz);
-        if (G > 3 && g == 3) skip_pick<(G > 3 ? 3 * SG : 0), (G > 3 ? 4 * SG : SG)>(ws + 3 * SG, wl, px, py, pz, sx, sy, sz);
+        if (g == 0) fps_pick_slot<0, SG>(ws, wl, px, py, pz, sx, sy, sz);
+        if (G > 1 && g == 1) fps_pick_slot<(G > 1 ? SG : 0), (G > 1 ? 2 * SG : SG)>(ws + SG, wl, px, py, pz, sx, sy, sz);
+        if (G > 2 && g == 2) fps_pick_slot<(G > 2 ? 2 * SG : 0), (G > 2 ? 3 * SG : SG)>(ws + 2 * SG, wl, px, py, pz, sx, sy, sz);
+        if (G > 3 && g == 3) fps_pick_slot<(G > 3 ? 3 * SG : 0), (G > 3 ? 4 * SG : SG)>(ws + 3 * SG, wl, px, py, pz, sx, sy, sz);
         cg_x[g] = sx; cg_y[g] = sy; cg_z[g] = sz;
       }
     }
@@ -324,7 +267,7 @@ __global__ __launch_bounds__(64 * NW) void fps_skip_kernel(int n, int m, int log
     int cw_k = cg_k[0];
 #pragma unroll
     for (int g = 1; g < G; ++g) {
-      const bool better = cg_val[g] > cw_val || (cg_val[g] == cw_val && tie_key(cg_k[g], log2s) < tie_key(cw_k, log2s));
+      const bool better = cg_val[g] > cw_val || (cg_val[g] == cw_val && fps_tie_key(cg_k[g], log2s) < fps_tie_key(cw_k, log2s));
       if (better) { cw_val = cg_val[g]; cw_k = cg_k[g]; cw_x = cg_x[g]; cw_y = cg_y[g]; cw_z = cg_z[g]; }
     }
     // 3. block arg-max over the waves' cached maxima
@@ -340,7 +283,7 @@ __global__ __launch_bounds__(64 * NW) void fps_skip_kernel(int n, int m, int log
     const float bmax = d6_row_max16(v2);      // 4 DPP steps instead of the 6 of a full-wave maximum
     const unsigned long long tie2 = __ballot(v2 == bmax) & ((1ull << NW) - 1ull);
     int ww = __builtin_ctzll(tie2);
-    if (__popcll(tie2) != 1) ww = min_key_lane(tie2, i2, log2s);
+    if (__popcll(tie2) != 1) ww = fps_min_key_lane(tie2, i2, log2s);
     const int old = d6_readlane_i(i2, ww);
     cx = d6_readlane_f(x2, ww);
     cy = d6_readlane_f(y2, ww);
@@ -361,11 +304,6 @@ extern "C" __attribute__((visibility("default"))) int det6d_dbg_fps_clock(unsign
 }
 #endif
 
-// fps_seq.hip: the multi-pick sampler
-int det6d_fps_seq_launch(int b, int n, int m, int log2s, long long xyz_bstride, long long idx_bstride, int idx_add,
-                         const float *xyz, const int *perm, int *idx, hipStream_t stream);
-
-// Called by fps.hip's launcher for D-FPS of 16384- and 4096-point scenes with fresh min-distances.  `perm` is (B, n) int32 scratch.
 // k-d order (4 x 4 cells of equal counts, lanes ordered by the tie key) of every 16384-point part src[g] of `subscenes`
 // scene parts (fps_coop.hip); perm[g] = the part's points in that order
 int det6d_fps_cell_sort_parts(int subscenes, int parts, int log2s, long long xyz_bstride, const float *xyz, const int *src, int *perm,
@@ -374,6 +312,7 @@ int det6d_fps_cell_sort_parts(int subscenes, int parts, int log2s, long long xyz
   return det6d_check_launch("det6d_fps (cooperative: k-d order of the parts)");
 }
 
+// Called by fps.hip's launcher for D-FPS of 16384- and 4096-point scenes with fresh min-distances.  `perm` is (B, n) int32 scratch.
 int det6d_fps_cells_launch(int b, int n, int m, int log2s, long long xyz_bstride, long long idx_bstride, int idx_add,
                            const float *xyz, int *perm, int *idx, hipStream_t stream) {
   if (n != 16384 && n != 4096) return DET6D_EINVAL;
@@ -398,9 +337,6 @@ int det6d_fps_cells_launch(int b, int n, int m, int log2s, long long xyz_bstride
 }
 
 // the score-weighted form: k-d pre-pass (a permutation of the scene: the weights play no part in it) + fps_seq_w_kernel
-int det6d_fps_seq_w_launch(int b, int n, int m, int log2s, long long xyz_bstride, long long idx_bstride, int idx_add,
-                           const float *xyz, const int *perm, int *idx, const float *weights, long long w_bstride, float gamma,
-                           int w_is_score, int *flags, hipStream_t stream);      // fps_seq.hip
 int det6d_fps_cells_w_launch(int b, int n, int m, int log2s, long long xyz_bstride, long long idx_bstride, int idx_add,
                              const float *xyz, int *perm, int *idx, const float *weights, long long w_bstride, float gamma,
                              int w_is_score, hipStream_t stream) {

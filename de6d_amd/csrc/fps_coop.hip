@@ -31,6 +31,7 @@
 // A part that waits longer than ~2 s for a partner (it can only be a scheduling accident) raises the error word of the
 // workspace, completes the scene's picks with a valid index and leaves: det6d_fps_fused_status reports the launch as failed
 // instead of the GPU hanging.
+#include "fps_common.h"
 #include "fps_multi.h"
 
 namespace {
@@ -42,25 +43,6 @@ constexpr int kMultiCands = 4;  // candidates per wave record of the multi-pick 
 // 64-bit words of one scene's exchange area in the multi-pick kernel: round-0 words + two parities of candidate words
 __host__ __device__ constexpr size_t coop_multi_words(int parts, int k) { return (size_t)8 * parts + (size_t)2 * parts * 16 * k * 5; }
 
-__device__ __forceinline__ unsigned co_bitrev_bits(unsigned v, int bits) {
-  return bits == 0 ? 0u : (__builtin_bitreverse32(v) >> (32 - bits));
-}
-// order key of point k under the reference's tie rule (smaller wins): (bitrev_{log2 S}(k mod S), k)
-__device__ __forceinline__ unsigned co_tie_key(int k, int log2s) {
-  return (co_bitrev_bits((unsigned)k & ((1u << log2s) - 1u), log2s) << (32 - log2s)) | ((unsigned)k >> log2s);
-}
-__device__ __forceinline__ int co_min_key_lane(unsigned long long cand, int k, int log2s) {
-  const int lane = threadIdx.x & 63;
-  const bool mine = (cand >> lane) & 1ull;
-  unsigned key = mine ? co_tie_key(k, log2s) : 0xFFFFFFFFu;
-  unsigned m = key;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const unsigned o = (unsigned)__shfl_xor((int)m, off);
-    m = o < m ? o : m;
-  }
-  return __builtin_ctzll(__ballot(mine && key == m));
-}
 // ---- pre-pass 1: the scene cut into PARTS spatial parts of exactly 16384 points (PARTS = 4: two halves by x, each cut in two
 // by y; PARTS = 2: two halves by x); clears the exchange area.  Counting partition in LDS: a histogram over 4096 bins of the
 // coordinate, an exclusive scan, one returning atomic per point for its position; the position decides the half — exact equal
@@ -69,22 +51,6 @@ __device__ __forceinline__ int co_min_key_lane(unsigned long long cand, int k, i
 // points, which cell_sort_kernel<16> (fps_cells.hip) then puts into the 4 x 4 k-d order of the single-workgroup sampler.
 // (Rounds 2-4: 20-bit Morton keys + hipcub::DeviceRadixSort over all scenes + a lane-ordering kernel: 8 launches.)
 constexpr int kSplitBins = 4096;
-
-__device__ __forceinline__ unsigned co_block_exclusive_sum(unsigned v, unsigned *__restrict__ wtot) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned o = (unsigned)__shfl_up((int)incl, off);
-    if (lane >= off) incl += o;
-  }
-  if (lane == 63) wtot[wave] = incl;
-  __syncthreads();
-  unsigned base = 0u;
-  for (int w = 0; w < wave; ++w) base += wtot[w];
-  __syncthreads();
-  return base + incl - v;
-}
 
 template <int PARTS>
 __global__ __launch_bounds__(1024) void coop_split_kernel(int n, long long xyz_bstride, const float *__restrict__ xyz,
@@ -126,7 +92,7 @@ __global__ __launch_bounds__(1024) void coop_split_kernel(int n, long long xyz_b
     unsigned c[4], total = 0u;
 #pragma unroll
     for (int q = 0; q < 4; ++q) { c[q] = bins[tid * 4 + q]; total += c[q]; }
-    unsigned base = co_block_exclusive_sum(total, wtot);
+    unsigned base = fps_block_exclusive_sum_1024(total, wtot);
 #pragma unroll
     for (int q = 0; q < 4; ++q) { bins[tid * 4 + q] = base; base += c[q]; }
   }
@@ -152,7 +118,7 @@ __global__ __launch_bounds__(1024) void coop_split_kernel(int n, long long xyz_b
       unsigned c[8], total = 0u;
 #pragma unroll
       for (int q = 0; q < 8; ++q) { c[q] = bins[tid * 8 + q]; total += c[q]; }
-      unsigned base = co_block_exclusive_sum(total, wtot);
+      unsigned base = fps_block_exclusive_sum_1024(total, wtot);
 #pragma unroll
       for (int q = 0; q < 8; ++q) { bins[tid * 8 + q] = base; base += c[q]; }
     }
@@ -168,22 +134,6 @@ __global__ __launch_bounds__(1024) void coop_split_kernel(int n, long long xyz_b
   // (the error word of the workspace is STICKY: it is cleared when the workspace is created (zero-filled by the caller) and by
   // det6d_fps_fused_status once it has been read, never by a launch — a later launch must not hide an earlier failure)
 }
-
-template <int LO, int HI, int N>
-__device__ __forceinline__ void co_pick(int ws, int wl, const float (&px)[N], const float (&py)[N], const float (&pz)[N],
-                                        float &sx, float &sy, float &sz) {
-  if constexpr (HI - LO == 1) {
-    sx = d6_readlane_f(px[LO], wl);
-    sy = d6_readlane_f(py[LO], wl);
-    sz = d6_readlane_f(pz[LO], wl);
-  } else {
-    constexpr int MID = (LO + HI) / 2;
-    if (ws < MID) co_pick<LO, MID>(ws, wl, px, py, pz, sx, sy, sz);
-    else co_pick<MID, HI>(ws, wl, px, py, pz, sx, sy, sz);
-  }
-}
-
-typedef float co_f32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ unsigned long long co_pack(unsigned payload, unsigned tag) {
   return ((unsigned long long)tag << 32) | payload;
@@ -289,14 +239,14 @@ __global__ __launch_bounds__(1024) void fps_coop_kernel(int b, int n, int m, int
     if (!(lb >= cg_val)) {
       float best = -1.0f;
       int bs = 0;
-      const co_f32x2 c2x = {cx, cx}, c2y = {cy, cy}, c2z = {cz, cz};
+      const fps_f32x2 c2x = {cx, cx}, c2y = {cy, cy}, c2z = {cz, cz};
 #pragma unroll
       for (int q = 0; q < HG; ++q) {
         const int s0 = 2 * q;
-        const co_f32x2 dx = co_f32x2{px[s0], px[s0 + 1]} - c2x;
-        const co_f32x2 dy = co_f32x2{py[s0], py[s0 + 1]} - c2y;
-        const co_f32x2 dz = co_f32x2{pz[s0], pz[s0 + 1]} - c2z;
-        co_f32x2 d = dy * dy;
+        const fps_f32x2 dx = fps_f32x2{px[s0], px[s0 + 1]} - c2x;
+        const fps_f32x2 dy = fps_f32x2{py[s0], py[s0 + 1]} - c2y;
+        const fps_f32x2 dz = fps_f32x2{pz[s0], pz[s0 + 1]} - c2z;
+        fps_f32x2 d = dy * dy;
         d = __builtin_elementwise_fma(dx, dx, d);
         d = __builtin_elementwise_fma(dz, dz, d);
 #pragma unroll
@@ -313,11 +263,11 @@ __global__ __launch_bounds__(1024) void fps_coop_kernel(int b, int n, int m, int
       const unsigned long long tie = __ballot(best == wmax);
       int wl = __builtin_ctzll(tie);
       const int gbase = wave * 64;
-      if (__popcll(tie) != 1) wl = co_min_key_lane(tie, (int)korig[(gbase + lane) * SLOTS + bs], log2s);
+      if (__popcll(tie) != 1) wl = fps_min_key_lane(tie, (int)korig[(gbase + lane) * SLOTS + bs], log2s);
       const int ws = d6_readlane_i(bs, wl);
       cg_val = wmax;
       cg_k = (int)korig[(gbase + wl) * SLOTS + ws];
-      co_pick<0, SLOTS>(ws, wl, px, py, pz, cg_x, cg_y, cg_z);
+      fps_pick_slot<0, SLOTS>(ws, wl, px, py, pz, cg_x, cg_y, cg_z);
     }
     // 2. this part's arg-max over its waves' cached maxima
     if (lane == 0) {
@@ -331,7 +281,7 @@ __global__ __launch_bounds__(1024) void fps_coop_kernel(int b, int n, int m, int
     const float bmax = d6_row_max16(e2.x);
     const unsigned long long tie2 = __ballot(e2.x == bmax) & ((1ull << NW) - 1ull);
     int ww = __builtin_ctzll(tie2);
-    if (__popcll(tie2) != 1) ww = co_min_key_lane(tie2, i2, log2s);
+    if (__popcll(tie2) != 1) ww = fps_min_key_lane(tie2, i2, log2s);
     const int pk = d6_readlane_i(i2, ww);
     const float pxw = d6_readlane_f(e2.y, ww), pyw = d6_readlane_f(e2.z, ww), pzw = d6_readlane_f(e2.w, ww);
     // 3. publish (wave 0), then every wave polls the PARTS slots of this round
@@ -374,7 +324,7 @@ __global__ __launch_bounds__(1024) void fps_coop_kernel(int b, int n, int m, int
     const float gmax = d6_row_max16(vv);
     const unsigned long long tie3 = __ballot(vv == gmax) & ((1ull << PARTS) - 1ull);
     int wp = __builtin_ctzll(tie3);
-    if (__popcll(tie3) != 1) wp = co_min_key_lane(tie3, k2, log2s);
+    if (__popcll(tie3) != 1) wp = fps_min_key_lane(tie3, k2, log2s);
     const int old = d6_readlane_i(k2, wp);
     cx = d6_readlane_f(x2, wp);
     cy = d6_readlane_f(y2, wp);
@@ -556,7 +506,7 @@ __global__ __launch_bounds__(1024) void fps_coop_multi_kernel(int b, int n, int 
         const int nc = (int)(((unsigned)w1 >> 16) & 7u);
         const int slot = lane & (K - 1);
         cv[s_] = slot < nc ? __builtin_bit_cast(float, (unsigned)w0) : -1.0f;
-        ntk[s_] = ~sq_tie_key((int)((unsigned)w1 & 0xFFFFu), log2s);      // ~tie key: larger wins
+        ntk[s_] = ~fps_tie_key((int)((unsigned)w1 & 0xFFFFu), log2s);      // ~tie key: larger wins
         qx[s_] = __builtin_bit_cast(float, (unsigned)w2);
         qy[s_] = __builtin_bit_cast(float, (unsigned)w3);
         qz[s_] = __builtin_bit_cast(float, (unsigned)w4);
@@ -613,7 +563,7 @@ __global__ __launch_bounds__(1024) void fps_coop_multi_kernel(int b, int n, int 
           }
           const u64 tie = __ballot(lkey == best);
           int wl = __builtin_ctzll(tie);
-          if (__popcll(tie) != 1) wl = sq_min_key_lane(tie, ~(unsigned)lbest);
+          if (__popcll(tie) != 1) wl = fps_min_key_lane(tie, ~(unsigned)lbest);
           const float sx = d6_readlane_f(ex, wl), sy = d6_readlane_f(ey, wl), sz = d6_readlane_f(ez, wl);
           {
             int ls = lset;
@@ -621,13 +571,13 @@ __global__ __launch_bounds__(1024) void fps_coop_multi_kernel(int b, int n, int 
             mws = lane == j ? ((d6_readlane_i(ls, wl) << 6) | wl) : mws;
           }
           if constexpr (SETS % 2 == 0) {
-            const sq_f32x2 c2x = {sx, sx}, c2y = {sy, sy}, c2z = {sz, sz};
+            const fps_f32x2 c2x = {sx, sx}, c2y = {sy, sy}, c2z = {sz, sz};
 #pragma unroll
             for (int s_ = 0; s_ < SETS; s_ += 2) {
-              const sq_f32x2 dx = sq_f32x2{qx[s_], qx[s_ + 1]} - c2x;
-              const sq_f32x2 dy = sq_f32x2{qy[s_], qy[s_ + 1]} - c2y;
-              const sq_f32x2 dz = sq_f32x2{qz[s_], qz[s_ + 1]} - c2z;
-              sq_f32x2 d = dy * dy;
+              const fps_f32x2 dx = fps_f32x2{qx[s_], qx[s_ + 1]} - c2x;
+              const fps_f32x2 dy = fps_f32x2{qy[s_], qy[s_ + 1]} - c2y;
+              const fps_f32x2 dz = fps_f32x2{qz[s_], qz[s_ + 1]} - c2z;
+              fps_f32x2 d = dy * dy;
               d = __builtin_elementwise_fma(dx, dx, d);
               d = __builtin_elementwise_fma(dz, dz, d);
               cv[s_] = d6_vmin(cv[s_], d[0]);
@@ -652,7 +602,7 @@ __global__ __launch_bounds__(1024) void fps_coop_multi_kernel(int b, int n, int 
           }
           if (lane < j) {
             pick_x[lane] = mx; pick_y[lane] = my; pick_z[lane] = mz;
-            if (part == 0) idxs[r + lane] = sq_tie_key_point(~mtk, log2s) + idx_add;
+            if (part == 0) idxs[r + lane] = fps_tie_key_point(~mtk, log2s) + idx_add;
           }
         }
       }
@@ -690,11 +640,6 @@ long long det6d_fps_coop_workspace_bytes(int b, int n) {
   return (long long)coop_layout(b, n).total;
 }
 
-// D-FPS of b scenes of n = 32768 / 65536 points with fresh min-distances; `workspace` of
-// det6d_fps_coop_workspace_bytes(b, n) bytes (256-byte aligned)
-int det6d_fps_cell_sort_parts(int subscenes, int parts, int log2s, long long xyz_bstride, const float *xyz, const int *src, int *perm,
-                              hipStream_t stream);      // fps_cells.hip
-
 // CU count of the CURRENT device (cached per device: a process may drive several)
 static int coop_device_cus() {
   static int cus_of[64] = {0};
@@ -714,6 +659,8 @@ bool det6d_fps_coop_fits_device(int n) {
   return det6d_fps_coop_handles(n) && coop_device_cus() >= 8 * (n / kPartPoints);
 }
 
+// D-FPS of b scenes of n = 32768 / 65536 points with fresh min-distances; `workspace` of
+// det6d_fps_coop_workspace_bytes(b, n) bytes (256-byte aligned)
 int det6d_fps_coop_launch(int b, int n, int m, int log2s, long long xyz_bstride, long long idx_bstride, int idx_add,
                           const float *xyz, void *workspace, int *idx, hipStream_t stream) {
   if (!det6d_fps_coop_handles(n) || b <= 0 || b > 4096 || !workspace || ((uintptr_t)workspace & 255)) return DET6D_EINVAL;

@@ -1,47 +1,18 @@
-// fps_multi.h — pieces shared by the multi-pick farthest point samplers (fps_seq.hip: one workgroup per 16384-point scene,
-// experiments build; fps_coop.hip: 2 / 4 cooperating workgroups per 32768 / 65536-point scene): the record a wave publishes
-// after a rescan (its top K points in the reference's order), the rescan that extracts it, and the cross-lane reductions of
-// the sequencer.  The decision rule is described at the top of fps_seq.hip; tests/models/fps_lookahead.py is its executable
-// model.
+// fps_multi.h — what is specific to the multi-pick farthest point samplers (fps_seq.hip: one workgroup per 16384- / 4096-point
+// scene, the shipped D-FPS / S-FPS of those sizes; fps_coop.hip: 2 / 4 cooperating workgroups per 32768 / 65536-point scene):
+// the record a wave publishes after a rescan (its top K points in the reference's order), the rescan that extracts it, and
+// the cross-lane group reductions of the sequencer.  The tie rule and the helpers every sampler shares: fps_common.h.  The
+// decision rule is described at the top of fps_seq.hip; tests/models/fps_lookahead.py is its executable model.
 #pragma once
-#include "common.h"
+#include "fps_common.h"
 
 namespace {
-
-typedef unsigned long long u64;
-typedef float sq_f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kCandMax = 4;              // candidates per record = sequencer lanes per region (2 or 4)
 constexpr int kWaves = 16, kSlots = 16;  // 16 x 64 x 16 = 16384 points
 constexpr int kMaxPicks = 32;            // picks per round at most (one workgroup per scene)
 constexpr int kCoopMaxPicks = 64;        // ... of the cooperative form (one per lane of the owners' box test)
 static_assert(kWaves * kCandMax == 64, "one sequencer lane per candidate");
-
-__device__ __forceinline__ unsigned sq_bitrev_bits(unsigned v, int bits) {
-  return bits == 0 ? 0u : (__builtin_bitreverse32(v) >> (32 - bits));
-}
-// order key of point k under the reference's tie rule (smaller wins): (bitrev_{log2 S}(k mod S), k)
-__device__ __forceinline__ unsigned sq_tie_key(int k, int log2s) {
-  return (sq_bitrev_bits((unsigned)k & ((1u << log2s) - 1u), log2s) << (32 - log2s)) | ((unsigned)k >> log2s);
-}
-// the point a tie key belongs to
-__device__ __forceinline__ int sq_tie_key_point(unsigned key, int log2s) {
-  if (log2s == 0) return (int)key;
-  return (int)(((key & ((1u << (32 - log2s)) - 1u)) << log2s) | sq_bitrev_bits(key >> (32 - log2s), log2s));
-}
-// lane holding the smallest key among the lanes of `cand` (tie path only)
-__device__ __forceinline__ int sq_min_key_lane(u64 cand, unsigned key) {
-  const int lane = threadIdx.x & 63;
-  const bool mine = (cand >> lane) & 1ull;
-  const unsigned k = mine ? key : 0xFFFFFFFFu;
-  unsigned m = k;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const unsigned o = (unsigned)__shfl_xor((int)m, off);
-    m = o < m ? o : m;
-  }
-  return __builtin_ctzll(__ballot(mine && k == m));
-}
 
 // slot ws (wave-uniform) of this lane's coordinate registers: scalar binary search down to the statically indexed slot.
 // (The empty asm in the leaf keeps the 16 leaves apart: without it the compiler merges them into ONE load with a computed
@@ -281,14 +252,14 @@ __device__ __forceinline__ void sq_hide_lane_duplicates_w(const float (&px)[SG],
 template <int SG>
 __device__ __forceinline__ void sq_apply(float cx, float cy, float cz, const float (&px)[SG], const float (&py)[SG],
                                          const float (&pz)[SG], float (&pt)[SG]) {
-  const sq_f32x2 c2x = {cx, cx}, c2y = {cy, cy}, c2z = {cz, cz};
+  const fps_f32x2 c2x = {cx, cx}, c2y = {cy, cy}, c2z = {cz, cz};
 #pragma unroll
   for (int q = 0; q < SG / 2; ++q) {
     const int s0 = 2 * q;
-    const sq_f32x2 dx = sq_f32x2{px[s0], px[s0 + 1]} - c2x;
-    const sq_f32x2 dy = sq_f32x2{py[s0], py[s0 + 1]} - c2y;
-    const sq_f32x2 dz = sq_f32x2{pz[s0], pz[s0 + 1]} - c2z;
-    sq_f32x2 d = dy * dy;
+    const fps_f32x2 dx = fps_f32x2{px[s0], px[s0 + 1]} - c2x;
+    const fps_f32x2 dy = fps_f32x2{py[s0], py[s0 + 1]} - c2y;
+    const fps_f32x2 dz = fps_f32x2{pz[s0], pz[s0 + 1]} - c2z;
+    fps_f32x2 d = dy * dy;
     d = __builtin_elementwise_fma(dx, dx, d);
     d = __builtin_elementwise_fma(dz, dz, d);
     pt[s0] = d6_vmin(d[0], pt[s0]);
@@ -308,7 +279,7 @@ __device__ __forceinline__ float sq_rescan(float cx, float cy, float cz, int log
   const int lane = threadIdx.x & 63;
   float best = -1.0f, sec = -1.0f;
   int bs = 0;
-  const sq_f32x2 c2x = {cx, cx}, c2y = {cy, cy}, c2z = {cz, cz};
+  const fps_f32x2 c2x = {cx, cx}, c2y = {cy, cy}, c2z = {cz, cz};
   auto visit = [&](int j, float d) {
     const float t = d6_vmin(d, pt[j]);
     pt[j] = t;
@@ -320,10 +291,10 @@ __device__ __forceinline__ float sq_rescan(float cx, float cy, float cz, int log
 #pragma unroll
   for (int q = 0; q < SG / 2; ++q) {
     const int s0 = 2 * q;
-    const sq_f32x2 dx = sq_f32x2{px[s0], px[s0 + 1]} - c2x;
-    const sq_f32x2 dy = sq_f32x2{py[s0], py[s0 + 1]} - c2y;
-    const sq_f32x2 dz = sq_f32x2{pz[s0], pz[s0 + 1]} - c2z;
-    sq_f32x2 d = dy * dy;
+    const fps_f32x2 dx = fps_f32x2{px[s0], px[s0 + 1]} - c2x;
+    const fps_f32x2 dy = fps_f32x2{py[s0], py[s0 + 1]} - c2y;
+    const fps_f32x2 dz = fps_f32x2{pz[s0], pz[s0 + 1]} - c2z;
+    fps_f32x2 d = dy * dy;
     d = __builtin_elementwise_fma(dx, dx, d);
     d = __builtin_elementwise_fma(dz, dz, d);
     visit(s0, d[0]);
@@ -359,7 +330,7 @@ __device__ __forceinline__ float sq_rescan(float cx, float cy, float cz, int log
     if (__popcll(tie) != 1) {                              // equal heads: the reference's key decides
       if (__ballot(taken != 0 && head == wm) != 0ull) { ss = second_slot(); have_ss = true; }
       const int hs = taken ? ss : bs;
-      wl = sq_min_key_lane(tie, sq_tie_key((int)korig_w[lane * SG + hs], log2s));
+      wl = fps_min_key_lane(tie, fps_tie_key((int)korig_w[lane * SG + hs], log2s));
     }
     const int wtk = d6_readlane_i(taken, wl);
     int ws;
@@ -398,7 +369,7 @@ __device__ __forceinline__ float sq_rescan_w(float cx, float cy, float cz, int l
   const int lane = threadIdx.x & 63;
   float best = -1.0f, sec = -1.0f, tm = 0.f;
   int bs = 0;
-  const sq_f32x2 c2x = {cx, cx}, c2y = {cy, cy}, c2z = {cz, cz};
+  const fps_f32x2 c2x = {cx, cx}, c2y = {cy, cy}, c2z = {cz, cz};
   auto visit = [&](int j, float d) {
     const float t = d6_vmin(d, pt[j]);
     pt[j] = t;
@@ -412,10 +383,10 @@ __device__ __forceinline__ float sq_rescan_w(float cx, float cy, float cz, int l
 #pragma unroll
   for (int q = 0; q < SG / 2; ++q) {
     const int s0 = 2 * q;
-    const sq_f32x2 dx = sq_f32x2{px[s0], px[s0 + 1]} - c2x;
-    const sq_f32x2 dy = sq_f32x2{py[s0], py[s0 + 1]} - c2y;
-    const sq_f32x2 dz = sq_f32x2{pz[s0], pz[s0 + 1]} - c2z;
-    sq_f32x2 d = dy * dy;
+    const fps_f32x2 dx = fps_f32x2{px[s0], px[s0 + 1]} - c2x;
+    const fps_f32x2 dy = fps_f32x2{py[s0], py[s0 + 1]} - c2y;
+    const fps_f32x2 dz = fps_f32x2{pz[s0], pz[s0 + 1]} - c2z;
+    fps_f32x2 d = dy * dy;
     d = __builtin_elementwise_fma(dx, dx, d);
     d = __builtin_elementwise_fma(dz, dz, d);
     visit(s0, d[0]);
@@ -443,7 +414,7 @@ __device__ __forceinline__ float sq_rescan_w(float cx, float cy, float cz, int l
     if (__popcll(tie) != 1) {                              // equal heads: the reference's key decides
       if (__ballot(taken != 0 && head == wm) != 0ull) { ss = second_slot(); have_ss = true; }
       const int hs = taken ? ss : bs;
-      wl = sq_min_key_lane(tie, sq_tie_key((int)korig_w[lane * SG + hs], log2s));
+      wl = fps_min_key_lane(tie, fps_tie_key((int)korig_w[lane * SG + hs], log2s));
     }
     const int wtk = d6_readlane_i(taken, wl);
     int ws;

@@ -24,6 +24,7 @@
 // Two barriers per round; between them only wave 0 works (the other 15 sleep at the barrier: no issue slots taken from
 // co-resident GEMM waves).
 #include <stdio.h>
+#include "fps_common.h"
 #include "fps_multi.h"
 
 namespace {
@@ -164,7 +165,7 @@ __global__ __launch_bounds__(1024) void fps_seq_kernel(int n, int m, int log2s, 
       // first decision always goes through.)
       const unsigned ub = ((__builtin_bit_cast(unsigned, bound_v) << 1) | 1u) + 2u;
       const bool alive = live && slot < nc;
-      const unsigned ntk = ~sq_tie_key(kidx, log2s);                                  // larger = earlier in the order
+      const unsigned ntk = ~fps_tie_key(kidx, log2s);                                  // larger = earlier in the order
       const unsigned ntk_last = sq_group_max_u32<kCand>(is_last ? ntk : 0u);
       const unsigned thr = !alive ? 0xFFFFFFFFu : ntk >= ntk_last ? ub - 1u : ub;
       const unsigned alt = is_last ? ub : 0u;
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(1024) void fps_seq_kernel(int n, int m, int log2s, 
           const unsigned best = sq_wave_max_u32(key);
           const u64 tie = __ballot(key == best);
           int wl = __builtin_ctzll(tie);
-          if (__popcll(tie) != 1) wl = sq_min_key_lane(tie, ~ntk);
+          if (__popcll(tie) != 1) wl = fps_min_key_lane(tie, ~ntk);
           const float sx = d6_readlane_f(qx, wl), sy = d6_readlane_f(qy, wl), sz = d6_readlane_f(qz, wl);
           mwl = lane == j ? wl : mwl;
           cv = d6_vmin(cv, d6_sqdist(qx - sx, qy - sy, qz - sz));   // (an empty slot stays at -1)
@@ -303,8 +304,8 @@ __global__ __launch_bounds__(1024) void fps_seq_w_kernel(int n, int m, int log2s
     const float wm = d6_wave_max(small ? 0.f : bw);        // (a flagged scene leaves below: whatever this computes is dropped)
     const u64 tie = __ballot(bw == wm);
     int wl = tie ? __builtin_ctzll(tie) : 0;
-    const unsigned mykey = sq_tie_key((int)korig_w[lane * SG + bs0], log2s);
-    if (__popcll(tie) > 1) wl = sq_min_key_lane(tie, mykey);
+    const unsigned mykey = fps_tie_key((int)korig_w[lane * SG + bs0], log2s);
+    if (__popcll(tie) > 1) wl = fps_min_key_lane(tie, mykey);
     if (lane == wl) {
       float x, y, z;
       sq_select<0, SG>(bs0, px, py, pz, x, y, z);
@@ -321,11 +322,11 @@ __global__ __launch_bounds__(1024) void fps_seq_w_kernel(int n, int m, int log2s
     const float vm = d6_wave_max(v);
     const u64 tie = __ballot(mine && v == vm);
     int wl = __builtin_ctzll(tie);
-    if (__popcll(tie) > 1) wl = sq_min_key_lane(tie, key);
+    if (__popcll(tie) > 1) wl = fps_min_key_lane(tie, key);
     if (lane == wl) {
       pick_x[0] = w0_x[lane]; pick_y[0] = w0_y[lane]; pick_z[0] = w0_z[lane];
       pick_n = 1;
-      idxs[0] = sq_tie_key_point(key, log2s) + idx_add;
+      idxs[0] = fps_tie_key_point(key, log2s) + idx_add;
     }
   }
   sq_hide_lane_duplicates_w<SG>(px, py, pz, pw, pt);
@@ -373,7 +374,7 @@ __global__ __launch_bounds__(1024) void fps_seq_w_kernel(int n, int m, int log2s
       const bool is_last = live && slot == nc - 1;
       const float bound_v = sq_group_max<kCand>(is_last ? sv : -2.0f);   // SCORE of the record's last candidate (group-uniform)
       const unsigned ub = ((__builtin_bit_cast(unsigned, bound_v) << 1) | 1u) + 2u;
-      const unsigned ntk = ~sq_tie_key(kidx, log2s);                                  // larger = earlier in the order
+      const unsigned ntk = ~fps_tie_key(kidx, log2s);                                  // larger = earlier in the order
       const unsigned ntk_last = sq_group_max_u32<kCand>(is_last ? ntk : 0u);
       const unsigned thr = !alive ? 0xFFFFFFFFu : ntk >= ntk_last ? ub - 1u : ub;
       const unsigned alt = is_last ? ub : 0u;
@@ -388,7 +389,7 @@ __global__ __launch_bounds__(1024) void fps_seq_w_kernel(int n, int m, int log2s
           const unsigned best = sq_wave_max_u32(key);
           const u64 tie = __ballot(key == best);
           int wl = __builtin_ctzll(tie);
-          if (__popcll(tie) != 1) wl = sq_min_key_lane(tie, ~ntk);
+          if (__popcll(tie) != 1) wl = fps_min_key_lane(tie, ~ntk);
           const float sx = d6_readlane_f(qx, wl), sy = d6_readlane_f(qy, wl), sz = d6_readlane_f(qz, wl);
           mwl = lane == j ? wl : mwl;
           cv = d6_vmin(cv, d6_sqdist(qx - sx, qy - sy, qz - sz));
@@ -493,7 +494,8 @@ extern "C" __attribute__((visibility("default"))) int det6d_dbg_occupy(int block
 }
 #endif
 
-// Called by fps_cells.hip's launcher after the Morton sort and the lane-group ordering (groups of 16 positions).
+// Called by fps_cells.hip's launchers after the k-d pre-pass (cell_sort_kernel: lane groups of n / 1024 positions ordered by
+// tie key).
 int det6d_fps_seq_launch(int b, int n, int m, int log2s, long long xyz_bstride, long long idx_bstride, int idx_add,
                          const float *xyz, const int *perm, int *idx, hipStream_t stream) {
   if (n != 16384 && n != 4096) return DET6D_EINVAL;

@@ -12,8 +12,28 @@ Target assignment (:171-326, :387-407) exists for the argument combinations Det6
 assign_stack_targets_mask / assign_targets (class, box and encoded regression targets) and
 assign_training_targets(batch_dict), which labels the output of an eval forward the way the reference's training
 forward (:837-844, :872-876) would.  Nothing in it reads a result on the host: it can be captured into a graph.
-forward() in training mode, the set_ignore_flag=True variants, ASSIGN_METHOD: iou, the SASA labels, losses and
-centerness (:101-170, :328-385, :409-776) are not implemented and raise.
+The training loss (:101-155, :426-776 with loss_utils.py:10-235) is two launches of csrc/ext/head_loss.hip and one more for
+its gradient: build_losses, get_vote_layer_loss, generate_centerness_label, get_cls_layer_loss, get_box_layer_loss,
+get_corner_loss_lidar and get_loss(tb_dict=None) under the reference's names, all reading self.forward_ret_dict, which
+prepare_loss(batch_dict) fills from an eval forward plus gt_boxes the way the reference's training forward would (:823-876).
+get_loss returns a 0-d tensor with a graph: loss.backward() reaches point_vote_coords, point_cls_preds and point_reg_preds of
+forward_ret_dict (prepare_loss(batch_dict, requires_grad=True) makes them leaves).  Differences from the reference, all of them
+kept on purpose:
+  * tb_dict values are 0-d device tensors, not Python floats: nothing is read on the host, the call can be captured;
+  * labels are constants.  The reference has no detach at :310, so a gradient leaks from the encoded offset labels back into
+    the vote coordinates; here the labels come out of assign_training_targets without a graph;
+  * the centerness label turns the frame about z by the LAST column of point_box_labels, which for the nine-column labels is
+    rx, not rz.  That is the reference's behaviour (:463) and what its checkpoints were trained against;
+  * the corner term is added under the foreground mask with a select, so background rows contribute exactly 0 (the reference
+    indexes with a boolean mask under `if reg_weights.sum() > 0`, which reads the device); pitch and roll take no part in it
+    (the reference passes [:, 0:7]);
+  * the layer methods (get_*_layer_loss, generate_centerness_label, get_corner_loss_lidar) return values without a graph;
+    the gradient flows through get_loss.
+Out of scope, raising NotImplementedError with the key's name: LOSS_SASA_CONFIG, AXIS_ALIGNED_IOU_LOSS_REGULARIZATION,
+LOSS_CLS FocalLoss / WeightedCrossEntropy, LOSS_REG WeightedL1Loss, code_weights, pred_velo, coders other than
+PointBinResidual6DCoder, use_mean_size.
+forward() in training mode, the set_ignore_flag=True variants, ASSIGN_METHOD: iou and the SASA labels (:328-385) are not
+implemented and raise.
 Parameters live under the reference's names (vote_layers, SA_module.mlps, shared_fc_layer,
 cls_layers, reg_layers) so reference checkpoints load unchanged."""
 import torch
@@ -22,7 +42,7 @@ import torch.nn as nn
 from ...ops.pointnet2.pointnet2_batch import pointnet2_modules
 from ...ops.pointnet2.pointnet2_batch.pointnet2_modules import fold_sequential, rows_ld, round4, run_chain, to_device
 from ...ops_backend import fused
-from ....ops import box_targets
+from ....ops import box_targets, head_loss
 from ...utils import box_coder_utils
 
 
@@ -59,6 +79,7 @@ class PointHeadBox6DVote(nn.Module):
         self.forward_ret_dict = None
         self._folded = None
         self._extra_width = None
+        self._loss_spec = None
 
     @staticmethod
     def make_fc_layers(input_channels, output_channels, fc_list):
@@ -263,3 +284,125 @@ class PointHeadBox6DVote(nn.Module):
         return {'vote_cls_labels': vote['point_cls_labels'], 'vote_reg_labels': vote['point_reg_labels'],
                 'point_cls_labels': point['point_cls_labels'], 'point_reg_labels': point['point_reg_labels'],
                 'point_box_labels': point['point_box_labels']}
+
+    # ---- training loss (point_head_box6d_vote.py:101-155, :426-776) ----------------------------------------------------
+    def build_losses(self, losses_cfg):
+        """validates LOSS_CONFIG and keeps its scalars as the host array the kernels read; what is out of scope raises
+        NotImplementedError naming the key"""
+        if losses_cfg is None:
+            raise KeyError("LOSS_CONFIG is not set")
+        coder = self.box_coder
+        if not isinstance(coder, box_coder_utils.PointBinResidual6DCoder):
+            raise NotImplementedError("TARGET_CONFIG.BOX_CODER: %s (the loss is implemented for PointBinResidual6DCoder)"
+                                      % type(coder).__name__)
+        if getattr(coder, 'use_mean_size', False):
+            raise NotImplementedError("BOX_CODER_CONFIG.use_mean_size is not supported")
+        if getattr(coder, 'pred_velo', False):
+            raise NotImplementedError("BOX_CODER_CONFIG.pred_velo is not supported")
+        loss_cls = losses_cfg.get('LOSS_CLS', None)
+        if loss_cls not in ('WeightedBinaryCrossEntropyLoss', 'WeightedBinaryCrossEntropyLossWithCenterness'):
+            raise NotImplementedError("LOSS_CLS: %s is not implemented (WeightedBinaryCrossEntropyLoss[WithCenterness])" % loss_cls)
+        if losses_cfg.get('LOSS_REG', None) != 'WeightedSmoothL1Loss':
+            raise NotImplementedError("LOSS_REG: %s is not implemented (WeightedSmoothL1Loss)" % losses_cfg.get('LOSS_REG', None))
+        if losses_cfg.get('LOSS_SASA_CONFIG', None) is not None:
+            raise NotImplementedError("LOSS_SASA_CONFIG is not implemented")
+        if losses_cfg.get('AXIS_ALIGNED_IOU_LOSS_REGULARIZATION', False):
+            raise NotImplementedError("AXIS_ALIGNED_IOU_LOSS_REGULARIZATION is not implemented")
+        weights = losses_cfg.get('LOSS_WEIGHTS', None) or {}
+        if weights.get('code_weights', None) is not None:
+            raise NotImplementedError("LOSS_WEIGHTS.code_weights is not implemented")
+        corner = bool(losses_cfg.get('CORNER_LOSS_REGULARIZATION', False))
+        needed = [k for k in head_loss.WEIGHT_KEYS if k != 'point_corner_weight' or corner]
+        if not coder.ground_aware:
+            needed.remove('point_pitch_cls_weight')
+        missing = [k for k in needed if k not in weights]
+        if missing:
+            raise KeyError("LOSS_CONFIG.LOSS_WEIGHTS lacks %s" % ', '.join(missing))
+        reg_cfg = dict(losses_cfg.get('LOSS_REG_CONFIG', None) or {})
+        unknown = sorted(set(reg_cfg) - {'beta'})
+        if unknown:
+            raise NotImplementedError("LOSS_REG_CONFIG: %s is not implemented (beta)" % ', '.join(unknown))
+        cls_cfg = losses_cfg.get('LOSS_CLS_CONFIG', None)
+        centerness = 'WithCenterness' in loss_cls
+        self._loss_spec = head_loss.LossSpec(
+            self.num_class, coder.angle_bin_num, ground_aware=coder.ground_aware, centerness=centerness, corner=corner,
+            weights={k: weights[k] for k in head_loss.WEIGHT_KEYS if k in weights}, beta=reg_cfg.get('beta', 1.0 / 9.0),
+            centerness_min=cls_cfg['centerness_min'] if cls_cfg is not None else 0.0,
+            centerness_max=cls_cfg['centerness_max'] if cls_cfg is not None else 1.0)
+        return self._loss_spec
+
+    def _loss_inputs(self):
+        if self._loss_spec is None:
+            self.build_losses(self.model_cfg.get('LOSS_CONFIG', None))
+        ret = self.forward_ret_dict
+        if ret is None or 'point_cls_labels' not in ret:
+            raise RuntimeError("the loss reads forward_ret_dict: call prepare_loss(batch_dict) after an eval forward")
+        return self._loss_spec, (ret['point_vote_coords'], ret['vote_reg_labels'], ret['vote_cls_labels'],
+                                 ret['point_cls_preds'].view(-1, self.num_class), ret['point_cls_labels'].view(-1),
+                                 ret['point_reg_preds'], ret['point_reg_labels'], ret['point_box_labels'])
+
+    def _loss_forward(self):
+        spec, tensors = self._loss_inputs()
+        return head_loss.forward(spec, *(t.detach().contiguous() for t in tensors), per_point=True)
+
+    def prepare_loss(self, batch_dict, requires_grad=False):
+        """Fills forward_ret_dict with what the reference's training forward puts there (:823-876), for the batch_dict an eval
+        forward returned plus batch_dict['gt_boxes'] (B, M, 9 + 1): the five labels of assign_training_targets,
+        point_candidate_coords and point_vote_coords as (N, 3), beside the predictions forward() left.
+        requires_grad=True makes point_vote_coords, point_cls_preds and point_reg_preds leaves, so that get_loss()[0].backward()
+        leaves dL/d(prediction) in their .grad."""
+        ret = self.forward_ret_dict
+        if ret is None or 'point_reg_preds' not in ret:
+            raise RuntimeError("prepare_loss needs the forward_ret_dict of an eval forward")
+        ret.update(self.assign_training_targets(batch_dict))
+        ret['point_candidate_coords'] = batch_dict['point_candidate_coords'][:, 1:4].contiguous()
+        ret['point_vote_coords'] = batch_dict['point_vote_coords'][:, 1:4].contiguous()
+        for key in ('point_vote_coords', 'point_cls_preds', 'point_reg_preds'):
+            ret[key] = ret[key].detach().requires_grad_(requires_grad)
+        return ret
+
+    def get_vote_layer_loss(self, tb_dict=None):
+        """:426-446 -> (vote_loss_reg, tb_dict); tb_dict['vote_loss_reg'] is a 0-d device tensor"""
+        sums, _ = self._loss_forward()
+        tb_dict = {} if tb_dict is None else tb_dict
+        tb_dict.update({'vote_loss_reg': sums[head_loss.VOTE]})
+        return sums[head_loss.VOTE], tb_dict
+
+    @torch.no_grad()
+    def generate_centerness_label(self, point_base, point_box_labels, pos_mask, epsilon=1e-6):
+        """:448-482.  The frame is turned about z by the last column of point_box_labels, as in the reference."""
+        if epsilon != 1e-6:
+            raise NotImplementedError("generate_centerness_label: epsilon = %r (the kernel clamps at 1e-6)" % (epsilon,))
+        return head_loss.centerness_labels(point_base.contiguous(), point_box_labels.contiguous(), pos_mask.contiguous())
+
+    def get_corner_loss_lidar(self, pred_boxes, gt_boxes):
+        """:515-540 for (N, 7) boxes -> (N,)"""
+        assert pred_boxes.shape[0] == gt_boxes.shape[0]
+        if pred_boxes.shape[1] != 7 or gt_boxes.shape[1] != 7:
+            raise NotImplementedError("get_corner_loss_lidar takes (N, 7) boxes: pitch and roll take no part in the corner loss")
+        return head_loss.corner_loss(pred_boxes.detach().contiguous(), gt_boxes.detach().contiguous())
+
+    def get_cls_layer_loss(self, tb_dict=None):
+        """:542-576 -> (point_loss_cls (N,), cls_weights (N,), tb_dict); tb_dict['point_pos_num'] is a 0-d device tensor"""
+        sums, (loss_cls, _, _) = self._loss_forward()
+        labels = self.forward_ret_dict['point_cls_labels'].view(-1)
+        tb_dict = {} if tb_dict is None else tb_dict
+        tb_dict.update({'point_pos_num': sums[head_loss.N_POS]})
+        return loss_cls, (labels >= 0).float(), tb_dict
+
+    def get_box_layer_loss(self, tb_dict=None):
+        """:578-731 -> (point_loss_box (N,), reg_weights (N,), tb_dict)"""
+        _, (_, loss_box, _) = self._loss_forward()
+        labels = self.forward_ret_dict['point_cls_labels'].view(-1)
+        return loss_box, (labels > 0).float(), ({} if tb_dict is None else tb_dict)
+
+    def get_loss(self, tb_dict=None):
+        """:752-776 -> (point_loss, tb_dict): two launches, and one more when point_loss.backward() runs.  tb_dict holds 0-d
+        device tensors under the reference's keys."""
+        spec, t = self._loss_inputs()
+        loss, sums = head_loss.HeadLoss.apply(spec, t[0], t[3], t[5], t[1], t[2], t[4], t[6], t[7])
+        tb_dict = {} if tb_dict is None else tb_dict
+        tb_dict.update({'point_loss_vote': sums[head_loss.VOTE], 'point_loss_cls': sums[head_loss.CLS],
+                        'point_loss_box': sums[head_loss.BOX], 'vote_loss_reg': sums[head_loss.VOTE],
+                        'point_pos_num': sums[head_loss.N_POS]})
+        return loss, tb_dict

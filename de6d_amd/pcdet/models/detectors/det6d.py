@@ -1,5 +1,6 @@
 """Det6D detector (core/pcdet/models/detectors/det6d.py:4-30): backbone_3d -> point_head ->
-post_processing.  Inference only; the training loss branch (:14-30) is out of scope."""
+post_processing.  forward() is inference only.  get_training_loss(batch_dict) (:24-30) gives the point head's loss for the
+batch_dict of an eval forward plus gt_boxes; the backward of the network itself is out of scope."""
 from ...ops_backend import fused
 from .detector3d_template import Detector3DTemplate
 
@@ -25,3 +26,13 @@ class Det6D(Detector3DTemplate):
         for module in self.module_list:
             batch_dict = module(batch_dict)
         return self.post_processing_async(batch_dict)
+
+    def get_training_loss(self, batch_dict, requires_grad=False):
+        """(loss, tb_dict, disp_dict) of :24-30 for the batch_dict forward() or forward_async() filled, plus
+        batch_dict['gt_boxes'] (B, M, 9 + 1).  The reference reads the labels its training forward stored; here
+        PointHeadBox6DVote.prepare_loss assigns them first.  loss and the tb_dict values are 0-d device tensors; nothing is
+        read on the host."""
+        disp_dict = {}
+        self.point_head.prepare_loss(batch_dict, requires_grad=requires_grad)
+        loss_point, tb_dict = self.point_head.get_loss()
+        return loss_point, tb_dict, disp_dict

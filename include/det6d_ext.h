@@ -113,6 +113,81 @@ int det6d_ext_assign_targets9(int n_points, const float *points, int ld_points, 
                               int num_class, float central_radius, int *box_idx, long long *cls_labels, float *box_labels,
                               int ld_box_labels, int n_cols, det6d_stream_t stream);
 
+/* ------------------------------------------------------------------ training loss ------ */
+
+/* The training loss of PointHeadBox6DVote (point_head_box6d_vote.py:426-776 with loss_utils.py:10-235) and its gradient with
+ * respect to the predictions, for the PointBinResidual6DCoder code layout [6 offsets, angle_bin_num bin logits, angle_bin_num
+ * bin residuals, then pitch_cls, pitch_res with DET6D_HEAD_LOSS_GROUND_AWARE, else pitch], LOSS_REG WeightedSmoothL1Loss
+ * without code weights and LOSS_CLS WeightedBinaryCrossEntropyLoss[WithCenterness].  Executable model: tests/models/head_loss.py.
+ * Row r of every tensor is one point; all tensors are dense: vote_preds (n, 3) = the vote coordinates, vote_reg_labels (n, 3),
+ * vote_cls_labels (n) int64, cls_preds (n, num_class), cls_labels (n) int64 (-1 ignored, 0 background, c > 0 class c),
+ * reg_preds and reg_labels (n, code_size), box_labels (n, ld_box_labels) = [x, y, z, dx, dy, dz, rz, ...].
+ * With sl(d) = 0.5 d^2 / beta if |d| < beta else |d| - 0.5 beta (|d| itself when beta < 1e-5), pos = cls_label > 0,
+ * valid = cls_label >= 0, bce(x, t) = max(x, 0) - x t + log1p(exp(-|x|)):
+ *   vote_r = [vote_cls_label > 0] * sum_k sl(vote_preds - vote_reg_labels);
+ *   cen_r  = pos ? cbrt(max(rl * rw * rh, 1e-6)) : 0, the ratios min / max of the distances to the two faces along each axis
+ *            of the label box, in the frame turned about z by the LAST column of box_labels (rx for nine columns: the
+ *            reference's behaviour); t_r = cmin + (cmax - cmin) * cen_r with DET6D_HEAD_LOSS_CENTERNESS, else 1;
+ *   cls_r  = valid * w_cls * mean_c bce(cls_preds[c], pos and c == cls_label - 1 ? t_r : 0);
+ *   box_r  = pos * (w_off * sum_{k<6} sl(pred_k - label_k) + w_acls * (logsumexp(bin logits) - logit[lb])
+ *            + w_areg * sl(pred residual[lb] - label residual[lb]) + w_pcls * focal(pitch_cls))
+ *            + w_preg * pw * S * sl(pitch_res difference) + pos * w_corner * corner_r,
+ *            lb = the first maximum of the label's bin columns, focal(x) with t = the pitch_cls label:
+ *            (0.25 t + 0.75 (1 - t)) * pt^2 * bce(x, t), pt = t (1 - sigmoid x) + (1 - t) sigmoid x;
+ *            pw = pitch_cls label > 0 (ground aware) or pos (otherwise); S = max(#pos, 1) / max(#pw, 1);
+ *   corner_r (DET6D_HEAD_LOSS_CORNER) = mean over the 8 yaw-only corners of min(sum_xyz sl1(P - G), sum_xyz sl1(P - G')),
+ *            beta 1, P the corners of the decoded box (centre = offsets + vote point, sizes = exp, yaw = (db + residual[db])
+ *            * 2 pi / angle_bin_num, db = the first maximum of the bin logits), G those of box_labels[0 .. 6], G' of the
+ *            label turned by pi.  Rows that are not pos contribute exactly 0 (a select, never 0 * inf).
+ *   sums[VOTE] = w_vote * sum vote_r / max(#vote+, 1); sums[CLS] = sum cls_r / max(#valid, 1);
+ *   sums[BOX] = sum box_r / max(#pos, 1); sums[TOTAL] = their sum.
+ * Reduction: 128 rows per workgroup, shuffles over the wave, LDS over the waves, one record per workgroup in `workspace`,
+ * added in index order by a final launch: the same inputs give the same bits.  No floating-point atomics.
+ * cfg: DET6D_HEAD_LOSS_NCFG floats in HOST memory, read during the call (no upload): the eight loss weights in the order
+ * vote_reg, point_cls, point_offset_reg, point_angle_cls, point_angle_reg, point_pitch_cls, point_pitch_reg, point_corner,
+ * then beta, centerness_min, centerness_max, and zeros.
+ * loss_cls, loss_box (the per-point vectors cls_r and box_r) and centerness (cen_r), each (n), may be NULL.
+ * Limits: 0 <= n <= 2^24, 1 <= num_class <= 16, 1 <= angle_bin_num <= 32, 7 <= ld_box_labels <= 1024, cfg finite, beta >= 0,
+ * ws_bytes >= det6d_ext_head_loss_workspace_bytes(n).  n == 0: nothing is launched and nothing written. */
+enum {
+  DET6D_HEAD_LOSS_GROUND_AWARE = 1, DET6D_HEAD_LOSS_CENTERNESS = 2, DET6D_HEAD_LOSS_CORNER = 4      /* flags */
+};
+enum {
+  DET6D_HEAD_LOSS_CFG_BETA = 8, DET6D_HEAD_LOSS_CFG_CMIN = 9, DET6D_HEAD_LOSS_CFG_CMAX = 10, DET6D_HEAD_LOSS_NCFG = 16
+};
+enum {                                                                                               /* sums[] */
+  DET6D_HEAD_LOSS_TOTAL = 0, DET6D_HEAD_LOSS_VOTE = 1, DET6D_HEAD_LOSS_CLS = 2, DET6D_HEAD_LOSS_BOX = 3,
+  DET6D_HEAD_LOSS_N_VOTE_POS = 4, DET6D_HEAD_LOSS_N_POS = 5, DET6D_HEAD_LOSS_N_PITCH_POS = 6, DET6D_HEAD_LOSS_N_VALID = 7,
+  DET6D_HEAD_LOSS_INV_VOTE = 8, DET6D_HEAD_LOSS_INV_CLS = 9, DET6D_HEAD_LOSS_INV_BOX = 10, DET6D_HEAD_LOSS_PITCH_SCALE = 11,
+  DET6D_HEAD_LOSS_NSUMS = 16
+};
+long long det6d_ext_head_loss_workspace_bytes(int n);
+int det6d_ext_head_loss_forward(int n, int num_class, int angle_bin_num, int flags, const float *cfg, const float *vote_preds,
+                                const float *vote_reg_labels, const long long *vote_cls_labels, const float *cls_preds,
+                                const long long *cls_labels, const float *reg_preds, const float *reg_labels,
+                                const float *box_labels, int ld_box_labels, void *workspace, long long ws_bytes, float *sums,
+                                float *loss_cls, float *loss_box, float *centerness, det6d_stream_t stream);
+
+/* upstream * d sums[TOTAL] / d (vote_preds, cls_preds, reg_preds), one launch.  `sums` is what the forward wrote for the same
+ * inputs; grad_loss is ONE float in DEVICE memory (the upstream gradient autograd hands over).  Labels are constants.  The first
+ * maximum (decoded bin) and the min (corner branch) pass the gradient through the branch taken; the counts are constants; the
+ * corner term reaches the three centre offsets, the three log-sizes, the residual of the decoded bin, and vote_preds.
+ * d_vote (n, 3), d_cls (n, num_class), d_reg (n, code_size): any may be NULL, not all three.  Every row is written. */
+int det6d_ext_head_loss_backward(int n, int num_class, int angle_bin_num, int flags, const float *cfg, const float *vote_preds,
+                                 const float *vote_reg_labels, const long long *vote_cls_labels, const float *cls_preds,
+                                 const long long *cls_labels, const float *reg_preds, const float *reg_labels,
+                                 const float *box_labels, int ld_box_labels, const float *sums, const float *grad_loss,
+                                 float *d_vote, float *d_cls, float *d_reg, det6d_stream_t stream);
+
+/* The two pieces of the loss the head also offers on caller-supplied rows, by the same arithmetic:
+ * centerness[r] = pos_mask[r] ? cen_r : 0 for points (n, 3), box_labels (n, ld_box_labels) and a byte mask (generate_centerness_label);
+ * loss[r] = corner_r for pred_boxes (n, ld_pred) and gt_boxes (n, ld_gt), columns 0 .. 6 = [x, y, z, dx, dy, dz, rz]
+ * (get_corner_loss_lidar).  Limits: 0 <= n <= 2^24, 7 <= the row lengths <= 1024; n == 0 launches nothing. */
+int det6d_ext_centerness_labels(int n, const float *points, const float *box_labels, int ld_box_labels,
+                                const unsigned char *pos_mask, float *centerness, det6d_stream_t stream);
+int det6d_ext_corner_loss(int n, const float *pred_boxes, int ld_pred, const float *gt_boxes, int ld_gt, float *loss,
+                          det6d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@
 // Grid build: one workgroup per scene; cell counts / cursors live in LDS (<= 128 x 128 cells; when
 // the scene is larger than 128 cells across, the cell edge grows instead — still >= the radius).
 #include "common.h"
-#include "compact_parts.h"
+#include "compact_list.h"
 
 namespace {
 
@@ -562,8 +562,8 @@ DET6D_API int det6d_ball_query_pair_grid_lists(int b, int n, int m, float rin_a,
   if (sa && sa < smin_a) sa = smin_a;              // (as det6d_compact_groups_pair does)
   if (sb && sb < smin_b) sb = smin_b;
   if (det6d_compact_check_group(ns_a, smin_a, &sa) || det6d_compact_check_group(ns_b, smin_b, &sb)) return DET6D_EINVAL;
-  const CompactCountArgs count[2] = {{ns_a, smin_a, det6d_compact_split_tol(sa), hdr_a + 16},
-                                     {ns_b, smin_b, det6d_compact_split_tol(sb), hdr_b + 16}};
+  const CompactCountArgs count[2] = {{ns_a, smin_a, det6d_compact_split_tol(sa), hdr_a + kCompactHdrTable},
+                                     {ns_b, smin_b, det6d_compact_split_tol(sb), hdr_b + kCompactHdrTable}};
   return launch_grid_query(b, n, m, rin_a, rout_a, ns_a, rin_b, rout_b, ns_b, new_xyz, xyz, workspace, cnt_a, idx_a, cnt_b,
                            idx_b, false, count, (hipStream_t)stream, "det6d_ball_query_pair_grid_lists");
 }

@@ -9,17 +9,10 @@
 // is evaluated on the first s = 2^ceil(log2(cnt)) slots of each centre only (s >= smin; empty balls take
 // the smallest class: their rows are computed from the reference's idx = 0 and masked to zero as before).
 //
-// Row space: centres are binned by class s in {32, 16, 8, 4, 2, 1}; each class owns one contiguous region
-// of the compact row space, the classes in descending s, every region padded to a multiple of 128 rows
-// (one GEMM row tile holds a single class), centres in ascending order inside a region.
-//   hdr[0]      total rows (multiple of 128): the GEMMs read their row count HERE, on the device
-//   hdr[1 + c]  end of the region of class c (s = 32 >> c), c = 0..5;  hdr[6] == hdr[0]
-//   hdr[8]      sum of min(cnt, ns) (rows that carry information), hdr[9] rows before the 128-row alignment
-//   crow_p[r]   global point row (scene * n + neighbour index) row r gathers
-//   crow_c[r]   centre (scene * m + j) row r belongs to, bit 30 set when its ball is empty (pooled value = 0:
-//               pointnet2_modules.py:465-467), -1 for alignment rows (computed, never stored)
+// Row space, header words and row tags (hdr / crow_p / crow_c): compact_list.h, the one statement of the layout that this
+// file produces and the grouped-MLP kernels consume.
 #include "common.h"
-#include "compact_parts.h"
+#include "compact_list.h"
 
 namespace {
 
@@ -43,7 +36,7 @@ __global__ __launch_bounds__(256) void compact_count_kernel(int total, const Pai
   const GroupArgs &ga = pa.g[blockIdx.y];
   const int ns = ga.ns, smin = ga.smin, split = ga.split;
   const int *__restrict__ cnt = ga.cnt;
-  int *__restrict__ table = ga.hdr + 16;
+  int *__restrict__ table = ga.hdr + kCompactHdrTable;
   __shared__ int acc[kClasses + 1];
   const int tid = threadIdx.x, i = blockIdx.x * 256 + tid;
   if (tid <= kClasses) acc[tid] = 0;
@@ -73,7 +66,7 @@ __global__ __launch_bounds__(256) void compact_place_kernel(int total, int n, in
   const int *__restrict__ cnt = ga.cnt;
   const int *__restrict__ idx = ga.idx;
   int *__restrict__ hdr = ga.hdr;
-  const int *__restrict__ table = ga.hdr + 16;
+  const int *__restrict__ table = ga.hdr + kCompactHdrTable;
   int *__restrict__ crow_p = ga.crow_p;
   int *__restrict__ crow_c = ga.crow_c;
   __shared__ int h_all[kClasses + 1], h_before[kClasses];
@@ -125,13 +118,13 @@ __global__ __launch_bounds__(256) void compact_place_kernel(int total, int n, in
     }
     start[kClasses] = r;
     if (blockIdx.x == 0) {
-      hdr[0] = r;
-      for (int c = 0; c < kClasses; ++c) hdr[1 + c] = c + 1 < kClasses ? start[c + 1] : r;
-      hdr[7] = total;
-      hdr[8] = h_all[kClasses];
-      hdr[9] = unaligned;
-      hdr[10] = 0;                   // tile ticket and exit counter of the persistent group kernels (mlp_group.hip: g_draw_ticket)
-      hdr[11] = 0;
+      hdr[kCompactHdrLive] = r;
+      for (int c = 0; c < kClasses; ++c) hdr[kCompactHdrClassEnd + c] = c + 1 < kClasses ? start[c + 1] : r;
+      hdr[kCompactHdrCentres] = total;
+      hdr[kCompactHdrInfoRows] = h_all[kClasses];
+      hdr[kCompactHdrUnaligned] = unaligned;
+      hdr[kCompactHdrTicket] = 0;    // tile ticket and exit counter of the persistent group kernels (mlp_group.hip: g_draw_ticket)
+      hdr[kCompactHdrExit] = 0;
     }
   }
   __syncthreads();
@@ -169,8 +162,8 @@ __global__ __launch_bounds__(256) void compact_place_kernel(int total, int n, in
   __shared__ int rows_s[256], tag_s[256];
   {
     int tag = i;
-    if (ok && cnt[i] <= 0) tag |= 0x40000000;      // empty ball: pooled value 0
-    if (rows & (rows - 1)) tag |= 0x20000000;      // several parts: combine with an atomic max
+    if (ok && cnt[i] <= 0) tag |= kCompactTagEmpty;      // empty ball: pooled value 0
+    if (rows & (rows - 1)) tag |= kCompactTagSplit;      // several parts: combine with an atomic max
     rows_s[tid] = ok ? rows : 0;
     tag_s[tid] = tag;
   }
@@ -207,7 +200,7 @@ DET6D_API int det6d_compact_rows_capacity(int total_centres, int ns) {
   return (total_centres * ns + kClasses * 128 + 1023) & ~1023;   // a multiple of 8 row tiles: keeps the XCD-aware tile order
 }
 
-DET6D_API int det6d_compact_hdr_ints(int total_centres) { return 16 + (kClasses + 1) * (det6d_divup(total_centres, 256) + 1); }
+DET6D_API int det6d_compact_hdr_ints(int total_centres) { return kCompactHdrTable + (kClasses + 1) * (det6d_divup(total_centres, 256) + 1); }
 
 int det6d_compact_check_group(int ns, int smin, int *split) {
   if (ns != 1 && ns != 2 && ns != 4 && ns != 8 && ns != 16 && ns != 32) return DET6D_EINVAL;

@@ -9,11 +9,12 @@
 // which is bit for bit the oracle's chain.  This kernel is the second line: gather P rows through the ball-query /
 // compact row lists, three FMAs, shift, ReLU — HBM-bound (reads rows x C1 gathered, writes rows x C1).
 #include "common.h"
+#include "compact_list.h"
 
 namespace {
 
 struct ExpandArgs {
-  int rows;                    // dense: b * m * ns; compact: capacity (live count in hdr[0])
+  int rows;                    // dense: b * m * ns; compact: capacity (live count in the list header)
   int c1;                      // output columns (multiple of 4), written at out[r * ldo + 0 .. c1); [c1, ldo) zero-filled
   const float *p; int ldp; int pcol0;     // P (points, ldp), this group's columns start at pcol0
   const float *w; int ldw;     // the layer's folded weights: rows 0..2 are the coordinate rows
@@ -30,7 +31,7 @@ struct ExpandArgs {
 
 __global__ __launch_bounds__(256) void group_expand_kernel(const ExpandArgs g) {
   const int c4 = g.ldo >> 2;                       // float4 columns per output row (pad columns included)
-  const int live = g.hdr ? g.hdr[0] : g.rows;
+  const int live = g.hdr ? g.hdr[kCompactHdrLive] : g.rows;
   const long long total = (long long)live * c4;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int r = (int)(i / c4);
@@ -42,7 +43,7 @@ __global__ __launch_bounds__(256) void group_expand_kernel(const ExpandArgs g) {
     if (g.hdr) {
       const int tag = g.crow_c[r];
       real = tag >= 0;                               // alignment rows of the compact list: zeros
-      cj = tag & 0x1fffffff;
+      cj = d6_compact_centre(tag);
       prow = g.crow_p[r];
     } else {
       cj = r / g.ns;

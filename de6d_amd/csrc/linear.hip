@@ -18,6 +18,7 @@
 // before the MFMA block of the current one (register prefetch); 16.5 KB LDS -> several
 // workgroups per CU hide each other's barriers.
 #include "common.h"
+#include "compact_list.h"
 #include <stdlib.h>
 
 namespace {
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
   const int K = g.k, N = g.ncols;
   // compact (ragged) rows: the row count lives on the device (csrc/compact.hip), g.rows is the capacity the
   // grid was sized for; tiles past the live rows leave at once.  R is a multiple of 128 there.
-  const int R = g.hdr ? g.hdr[0] : g.rows;
+  const int R = g.hdr ? g.hdr[kCompactHdrLive] : g.rows;
   // XCD-aware tile order (1-D grid): workgroups are dealt round-robin over the 8 XCDs, each with its
   // own L2.  All column tiles of a row tile get consecutive slots on ONE XCD, so the A rows they share
   // are fetched into that L2 once instead of once per column tile (speed only, never correctness).
@@ -88,8 +89,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
   if (row0 >= R) return;
   // pooling width of this tile: fixed (dense rows) or the class of the compact region the tile lies in
   int pool = g.pool;
-  if (pool < 0)
-    pool = row0 < g.hdr[1] ? 32 : row0 < g.hdr[2] ? 16 : row0 < g.hdr[3] ? 8 : row0 < g.hdr[4] ? 4 : row0 < g.hdr[5] ? 2 : 1;
+  if (pool < 0) {   // d6_compact_class, with the region ends read one by one, as far as the comparison gets
+    const int *end = g.hdr + kCompactHdrClassEnd;
+    pool = row0 < end[0] ? 32 : row0 < end[1] ? 16 : row0 < end[2] ? 8 : row0 < end[3] ? 4 : row0 < end[4] ? 2 : 1;
+  }
 
   // ---- A loader: each thread owns rows (tid/4) [and (tid/4 + 64)], k-quad (tid%4) of the tile ----
   const int ar = tid >> 2, akq = tid & 3;
@@ -123,7 +126,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
         arow[i] = g.a + (size_t)g.crow_p[r] * g.lda;
         const int cj = g.crow_c[r];
         if (akq == 0 && cj >= 0) {
-          const float *c = g.ctr + (size_t)(cj & 0x1fffffff) * g.ldctr;
+          const float *c = g.ctr + (size_t)d6_compact_centre(cj) * g.ldctr;
           csub[i][0] = c[0]; csub[i][1] = c[1]; csub[i][2] = c[2];
         }
       } else {
@@ -308,9 +311,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
     }
   }
   // compact rows: the centre each of this lane's (up to four) pooled values belongs to, -1 = nothing to store
-  // (alignment rows, or another lane is the writer).  Rows of a 32x32 tile held by a lane: 8*qq + 4*kh + (0..3).
-  //   class 4: group = rows 8*qq + 4*kh .. +3, every lane writes its own four groups
-  //   class 8 / 16 / 32: the lane^32 exchange completes the group; lanes of half 0 write group qq / qq>>1 / 0
+  // (alignment rows, or another lane is the writer: d6_compact_out_row)
   int pre_ctr[TM][4];
   if (g.pool < 0 && pool >= 4) {
     const int khl = (tid & 63) >> 5;
@@ -319,12 +320,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
       const int rbase = row0 + wm * 32 * TM + 32 * i;
 #pragma unroll
       for (int qq = 0; qq < 4; ++qq) {
+        // the rule of d6_compact_out_row(pool, qq, khl), as a row and a predicate
         const int rsel = pool == 4 ? 8 * qq + 4 * khl : pool == 8 ? 8 * qq : pool == 16 ? 16 * (qq >> 1) : 0;
         const bool writer = pool == 4 || (khl == 0 && (pool == 8 || (pool == 16 && !(qq & 1)) || (pool == 32 && qq == 0)));
         int cj = -1;
         if (writer) cj = g.crow_c[rbase + rsel];
-        pre_ctr[i][qq] = cj < 0 ? -1 : (cj & 0x3fffffff);
-        pre_cnt[i][qq] = (cj & 0x40000000) ? 0 : 1;   // bit 30: empty ball
+        pre_ctr[i][qq] = cj < 0 ? -1 : (cj & (kCompactTagCentre | kCompactTagSplit));
+        pre_cnt[i][qq] = d6_compact_is_empty(cj) ? 0 : 1;
       }
     }
   }
@@ -519,10 +521,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
           const float raw = pool == 2 ? d6_vmax(acc[i][j][e], acc[i][j][e + 1]) : acc[i][j][e];
           const int cj = g.crow_c[rbase + (e & 3) + 8 * (e >> 2) + 4 * kh];
           if (cok && cj >= 0) {
-            const float val = (cj & 0x40000000) ? 0.f : relu_act(raw + sh, g.act);
-            float *dst = g.y + (size_t)(cj & 0x1fffffff) * g.ldy + g.col0 + col;
-            if (cj & 0x20000000) __hip_atomic_fetch_max(reinterpret_cast<int *>(dst), __builtin_bit_cast(int, val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else *dst = val;
+            const float val = d6_compact_is_empty(cj) ? 0.f : relu_act(raw + sh, g.act);
+            d6_compact_store(g.y + (size_t)d6_compact_centre(cj) * g.ldy + g.col0 + col, val, cj);
           }
         }
       }
@@ -561,11 +561,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
           const int cj = pre_ctr[i][qq];
           if (cok && cj >= 0) {
             const float val = pre_cnt[i][qq] > 0 ? relu_act(v[qq] + sh, g.act) : 0.f;
-            float *dst = g.y + (size_t)(cj & 0x1fffffff) * g.ldy + g.col0 + col;
-            // bit 29: the centre's rows are cut into several parts (compact.hip, split lists): maximum over the parts
-            // by an integer atomic max on the non-negative post-ReLU values (the buffer was zeroed)
-            if (cj & 0x20000000) __hip_atomic_fetch_max(reinterpret_cast<int *>(dst), __builtin_bit_cast(int, val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else *dst = val;
+            d6_compact_store(g.y + (size_t)d6_compact_centre(cj) * g.ldy + g.col0 + col, val, cj);
           }
         }
       }

@@ -18,6 +18,7 @@
 // Arithmetic is identical to three det6d_linear calls: every output is one ascending-k fmaf chain,
 // + shift, ReLU; masked max over the nsample rows.
 #include "common.h"
+#include "compact_list.h"
 #include <stdlib.h>
 
 namespace {
@@ -45,40 +46,20 @@ struct ChainArgs {
   const float *s1, *s2, *s3;  // shifts
   int k1, c1, c2, c3;         // true widths: k1 = lda, c1,c2 <= 32, c3 <= 64
   float *y; int ldy; int col0;
-  // compact (ragged) rows (csrc/compact.hip): live row count and class regions in hdr, one point row and one
-  // centre per compact row; rows = capacity then
+  // compact (ragged) rows (compact_list.h): live row count and class regions in hdr, one point row and one
+  // centre tag per compact row; rows = capacity then
   const int *hdr; const int *crow_p; const int *crow_c;
 };
 
-// compact rows: class (= pooling width) of the 32-row tile starting at row0; h[c] = end of the region of class 32 >> c
-__device__ __forceinline__ int compact_class(int row0, int h1, int h2, int h3, int h4, int h5) {
-  return row0 < h1 ? 32 : row0 < h2 ? 16 : row0 < h3 ? 8 : row0 < h4 ? 4 : row0 < h5 ? 2 : 1;
-}
-// row (inside a 32-row tile) whose centre owns pooled value qq of a lane in half kh, -1: another lane writes it.
-// A lane holds rows 8*qq + 4*kh + (0..3); class 4 groups end inside the lane, wider groups after the lane^32 exchange.
-__device__ __forceinline__ int compact_out_row(int s, int qq, int kh) {
-  if (s < 4) return -1;          // classes 1, 2: stored at once by compact_store_small
-  if (s == 4) return 8 * qq + 4 * kh;
-  if (kh) return -1;
-  if (s == 8) return 8 * qq;
-  if (s == 16) return (qq & 1) ? -1 : 8 * qq;
-  return qq == 0 ? 0 : -1;
-}
-// pooled value of one part of a centre: plain store, or (bit 29 of the row tag: the centre's rows are cut into several
-// parts, compact.hip) integer atomic max on the non-negative post-ReLU value into the zeroed buffer
-__device__ __forceinline__ void compact_store(float *dst, float val, int tag) {
-  if (tag & 0x20000000) __hip_atomic_fetch_max(reinterpret_cast<int *>(dst), __builtin_bit_cast(int, val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else *dst = val;
-}
 // classes 1 and 2: every accumulator (pair) of a 32x32 tile is a group of its own: stored at once (no pending slot).
-// tags[e] = centre tag of the row accumulator e of this lane holds (compact_row_tags).
-__device__ __forceinline__ void compact_store_small(const ChainArgs &g, const f32x16 &o, int s, const int (&tags)[16], int col, float sh) {
+// tags[e] = centre tag of the row accumulator e of this lane holds (chain_row_tags).
+__device__ __forceinline__ void chain_store_small(const ChainArgs &g, const f32x16 &o, int s, const int (&tags)[16], int col, float sh) {
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     if (s == 2 && (e & 1)) continue;
     const float raw = s == 2 ? d6_vmax(o[e], o[e + 1 < 16 ? e + 1 : e]) : o[e];
     const int tag = tags[e];
-    if (tag >= 0) compact_store(g.y + (size_t)(tag & 0x1fffffff) * g.ldy + g.col0 + col, (tag & 0x40000000) ? 0.f : d6_relu(raw + sh), tag);
+    if (tag >= 0) d6_compact_store(g.y + (size_t)d6_compact_centre(tag) * g.ldy + g.col0 + col, d6_compact_is_empty(tag) ? 0.f : d6_relu(raw + sh), tag);
   }
 }
 // Row tags of a tile from the lanes that loaded them (lane r and r + 32 hold the tag of row r): accumulator e of a lane in
@@ -86,23 +67,12 @@ __device__ __forceinline__ void compact_store_small(const ChainArgs &g, const f3
 // accumulator: round 2 re-read crow_c inside the epilogue, 16 dependent L2 round trips per column tile, and — the class
 // regions being contiguous — the workgroups that owned the tail of the list (classes 2 and 1) ran several times longer
 // than the others (the kernels' matrix pipes were busy 33-42 %: profiles/r03_beam_*).
-__device__ __forceinline__ void compact_row_tags(int my_tag, int kh, int (&tags)[16]) {
+__device__ __forceinline__ void chain_row_tags(int my_tag, int kh, int (&tags)[16]) {
 #pragma unroll
   for (int e = 0; e < 16; ++e) tags[e] = __shfl(my_tag, (e & 3) + 8 * (e >> 2) + 4 * kh);
 }
-// the four 4-row maxima of a lane -> pooled values of class s (in place; v[qq] valid where compact_out_row >= 0)
-__device__ __forceinline__ void compact_pool(float (&v)[4], int s) {
-  if (s == 4) return;
-#pragma unroll
-  for (int qq = 0; qq < 4; ++qq) v[qq] = d6_vmax(v[qq], __shfl_xor(v[qq], 32));
-  if (s == 16) {
-    v[0] = d6_vmax(v[0], v[1]);
-    v[2] = d6_vmax(v[2], v[3]);
-  } else if (s == 32) {
-    v[0] = d6_vmax(d6_vmax(v[0], v[1]), d6_vmax(v[2], v[3]));
-  }
-}
-
+// mlp_chain_kernel only: with d6_relu (common.h) in its place the compiler schedules that kernel differently (1118 -> 1241
+// lines of code), so the LDS kernel keeps the C form; the register kernels use d6_relu
 __device__ __forceinline__ float relu1(float v) { return v > 0.f ? v : 0.f; }
 
 // column of a gathered row [x - cx, y - cy, z - cz, f_0 ..] at position j of the oracle's fma chain (chain_k in
@@ -258,6 +228,58 @@ __global__ __launch_bounds__(64 * kChainWaves) void mlp_chain_kernel(const Chain
   }
 }
 
+// ---- what the two register chain kernels share ----
+
+// tag of the row whose centre owns pooled value qq of this lane in a tile of class sc (-1: another lane writes it), from
+// the lane that loaded it: lane r holds the tag cj of row r, so the list is not read a second time.  (References on purpose:
+// with cj, sc and kh by value one kernel's registers are assigned differently.)
+__device__ __forceinline__ int chain_pooled_tag(const int &cj, const int &sc, int qq, const int &kh) {
+  const int r = d6_compact_out_row(sc, qq, kh);
+  const int tg = __shfl(cj, r < 0 ? 0 : r);
+  return r >= 0 ? tg : -1;
+}
+
+// ReLU of the first `nreg` of a transposed layer's 16 accumulator registers (per lane: 16 channels of ONE row) -> the
+// activation fragments of the next layer's k-steps: frag[s] = {half0: channel 2s, half1: channel 2s + 1}
+__device__ __forceinline__ void chain_to_fragments(const f32x16 &a, float *frag, int nreg) {
+#pragma unroll
+  for (int G = 0; G < 4; ++G) {
+    if (4 * G >= nreg) break;
+    float t[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) t[e] = d6_relu(a[4 * G + e]);
+    // inline asm: this compiler drops the SECOND result of __builtin_amdgcn_permlane32_swap (seen in the ISA:
+    // the source register is reused right after the swap).  a = [a.lo | b.lo], b = [a.hi | b.hi] afterwards.
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1\n\tv_permlane32_swap_b32 %2, %3\n\ts_nop 1"
+                 : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));
+    frag[4 * G + 0] = t[0];   // channels 8G + 0, 1
+    frag[4 * G + 1] = t[2];   // channels 8G + 2, 3
+    frag[4 * G + 2] = t[1];   // channels 8G + 4, 5
+    frag[4 * G + 3] = t[3];   // channels 8G + 6, 7
+  }
+}
+
+// stores the pooled values of tile `pend_tile`, kept back for one iteration: pend[j] = column tile j; compact lists: one
+// value per pooled row of the lane (pend_oc = its tag, -1: none), dense rows: one value per centre of the tile
+template <int NS, bool COMPACT, int NT, int NP>
+__device__ __forceinline__ void chain_flush(const ChainArgs &g, const float (&pend)[NT][NP], const int (&pend_oc)[4],
+                                            int pend_tile, int l31) {
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    const int col = 32 * j + l31;
+    if (COMPACT) {
+#pragma unroll
+      for (int qq = 0; qq < 4; ++qq)
+        if (pend_oc[qq] >= 0) d6_compact_store(g.y + (size_t)d6_compact_centre(pend_oc[qq]) * g.ldy + g.col0 + col, pend[j][qq], pend_oc[qq]);
+    } else if (NS == 32) {
+      g.y[(size_t)pend_tile * g.ldy + g.col0 + col] = pend[j][0];
+    } else {
+      g.y[(size_t)(2 * pend_tile) * g.ldy + g.col0 + col] = pend[j][0];
+      g.y[(size_t)(2 * pend_tile + 1) * g.ldy + g.col0 + col] = pend[j][1];
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Register-resident variant for the widths Det6D's first SA layer uses ([4->16->16->32], [4->32->32->64]).
 //
@@ -282,10 +304,13 @@ __global__ __launch_bounds__(256) void mlp_chain_reg_kernel(const ChainArgs g) {
   int n_waves = (gridDim.x * blockDim.x) >> 6;
   int pk_end = 0;
   if (COMPACT) {
-    // the live tiles of a compact list go round the workgroups that are needed (one tile per wave at least): tile t -> wave
-    // t mod (active waves).  The class regions are contiguous (32-row parts first, single rows last) and the small classes
-    // have the dearest epilogue, so contiguous chunks per workgroup (round 2) left the tail of the list to a few workgroups.
-    const int wpw = blockDim.x >> 6, live = g.hdr[0] / 32;
+    // Compact lists: the grid is sized for the capacity but the list holds a fraction of it.  Only the workgroups that get
+    // at least kPackTiles tiles per wave stay (the others leave before they load or stage any weights), and the live tiles
+    // go round the waves that stay: tile t -> wave t mod (active waves).  The class regions are contiguous (32-row parts
+    // first, single rows last) and the small classes have the dearest epilogue, so every workgroup gets the same mix of
+    // classes: contiguous chunks per workgroup (round 2) left the tail of the list to a few workgroups.
+    // (The same lines open mlp_chain_wide_kernel: as a shared function they changed both kernels' code, LABNOTES.)
+    const int wpw = blockDim.x >> 6, live = g.hdr[kCompactHdrLive] / 32;
     int nb = (live + wpw * kPackTiles - 1) / (wpw * kPackTiles);
     if (nb > (int)gridDim.x) nb = gridDim.x;
     if ((int)blockIdx.x >= nb) return;
@@ -311,7 +336,7 @@ __global__ __launch_bounds__(256) void mlp_chain_reg_kernel(const ChainArgs g) {
   const float one_k0 = kh == 0 ? 1.f : 0.f;
 
   int h1 = 0, h2 = 0, h3 = 0, h4 = 0, h5 = 0;
-  if (COMPACT) { h1 = g.hdr[1]; h2 = g.hdr[2]; h3 = g.hdr[3]; h4 = g.hdr[4]; h5 = g.hdr[5]; }
+  if (COMPACT) d6_compact_class_ends(g.hdr, h1, h2, h3, h4, h5);
   const int ntiles = COMPACT ? pk_end : g.rows / 32;   // end of this wave's tile range
   const int *nb_idx = COMPACT ? g.crow_p : g.idx;   // per-row neighbour: point index inside the scene / global point row
   // the tile index is wave-uniform: kept in SGPRs so that the batch index (a division by m) is scalar work
@@ -337,18 +362,13 @@ __global__ __launch_bounds__(256) void mlp_chain_reg_kernel(const ChainArgs g) {
     if (COMPACT) {
       in.row = *reinterpret_cast<const float4 *>(g.a + (size_t)p * 4);
       const int cj = ix.cj;
-      const float *c = g.ctr + (size_t)(cj < 0 ? 0 : cj & 0x1fffffff) * g.ldctr;
+      const float *c = g.ctr + (size_t)(cj < 0 ? 0 : cj & kCompactTagCentre) * g.ldctr;
       in.cx = c[0]; in.cy = c[1]; in.cz = c[2];
       in.cnt0 = in.cnt1 = 0;
       in.tag = cj;
-      // tags of the rows whose centres own this lane's pooled values: held by lane `row` (no second load of the list)
-      const int sc = compact_class(t * 32, h1, h2, h3, h4, h5);
+      const int sc = d6_compact_class(t * 32, h1, h2, h3, h4, h5);
 #pragma unroll
-      for (int qq = 0; qq < 4; ++qq) {
-        const int r = compact_out_row(sc, qq, kh);
-        const int tg = __shfl(cj, r < 0 ? 0 : r);
-        in.oc[qq] = r >= 0 ? tg : -1;
-      }
+      for (int qq = 0; qq < 4; ++qq) in.oc[qq] = chain_pooled_tag(cj, sc, qq, kh);
       return in;
     }
     in.tag = 0;
@@ -369,22 +389,7 @@ __global__ __launch_bounds__(256) void mlp_chain_reg_kernel(const ChainArgs g) {
   float pend[NT3][COMPACT ? 4 : 2];
   int pend_oc[4] = {-1, -1, -1, -1};
   int pend_tile = -1;
-  auto flush = [&]() {
-#pragma unroll
-    for (int j = 0; j < NT3; ++j) {
-      const int col = 32 * j + l31;
-      if (COMPACT) {
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq)
-          if (pend_oc[qq] >= 0) compact_store(g.y + (size_t)(pend_oc[qq] & 0x1fffffff) * g.ldy + g.col0 + col, pend[j][qq], pend_oc[qq]);
-      } else if (NS == 32) {
-        g.y[(size_t)pend_tile * g.ldy + g.col0 + col] = pend[j][0];
-      } else {
-        g.y[(size_t)(2 * pend_tile) * g.ldy + g.col0 + col] = pend[j][0];
-        g.y[(size_t)(2 * pend_tile + 1) * g.ldy + g.col0 + col] = pend[j][1];
-      }
-    }
-  };
+  auto flush = [&]() { chain_flush<NS, COMPACT>(g, pend, pend_oc, pend_tile, l31); };   // bound here: a direct call compiles differently
   for (; tile < ntiles; tile += n_waves) {
     const TileIn cur = nxt;
     if (pend_tile >= 0) flush();
@@ -404,31 +409,14 @@ __global__ __launch_bounds__(256) void mlp_chain_reg_kernel(const ChainArgs g) {
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf1[1], kh ? x2 : x1, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf1[2], one_k0, acc, 0, 0, 0);
     float frag[16];   // frag[s] = activation fragment of k-step s: {half0: channel 2s, half1: channel 2s + 1}
-    auto to_fragments = [&](const f32x16 &a, int nreg) {
-#pragma unroll
-      for (int G = 0; G < 4; ++G) {
-        if (4 * G >= nreg) break;
-        float t[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) t[e] = d6_relu(a[4 * G + e]);
-        // inline asm: this compiler drops the SECOND result of __builtin_amdgcn_permlane32_swap (seen in the ISA:
-        // the source register is reused right after the swap).  a = [a.lo | b.lo], b = [a.hi | b.hi] afterwards.
-        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1\n\tv_permlane32_swap_b32 %2, %3\n\ts_nop 1"
-                     : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));
-        frag[4 * G + 0] = t[0];   // channels 8G + 0, 1
-        frag[4 * G + 1] = t[2];   // channels 8G + 2, 3
-        frag[4 * G + 2] = t[1];   // channels 8G + 4, 5
-        frag[4 * G + 3] = t[3];   // channels 8G + 6, 7
-      }
-    };
-    to_fragments(acc, S2);
+    chain_to_fragments(acc, frag, S2);
     // ---- layer 2 (transposed) ----
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0.f;
 #pragma unroll
     for (int s = 0; s < S2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf2[s], frag[s], acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf2[S2], one_k0, acc, 0, 0, 0);
-    to_fragments(acc, S3);
+    chain_to_fragments(acc, frag, S3);
     // ---- layer 3 (rows in the registers again), shift + ReLU + mask + max over the nsample rows ----
 #pragma unroll
     for (int j = 0; j < NT3; ++j) {
@@ -443,18 +431,18 @@ __global__ __launch_bounds__(256) void mlp_chain_reg_kernel(const ChainArgs g) {
       if (COMPACT) {
 #pragma unroll
         for (int qq = 0; qq < 4; ++qq) q[qq] = d6_vmax(d6_vmax(o[4 * qq], o[4 * qq + 1]), d6_vmax(o[4 * qq + 2], o[4 * qq + 3]));
-        const int sc = compact_class(tile * 32, h1, h2, h3, h4, h5);
+        const int sc = d6_compact_class(tile * 32, h1, h2, h3, h4, h5);
         if (sc < 4) {
           int tags[16];
-          compact_row_tags(cur.tag, kh, tags);
-          compact_store_small(g, o, sc, tags, col, sh3[j]);
+          chain_row_tags(cur.tag, kh, tags);
+          chain_store_small(g, o, sc, tags, col, sh3[j]);
 #pragma unroll
           for (int qq = 0; qq < 4; ++qq) pend[j][qq] = 0.f;
           continue;
         }
-        compact_pool(q, sc);
+        d6_compact_pool(q, sc);
 #pragma unroll
-        for (int qq = 0; qq < 4; ++qq) pend[j][qq] = (cur.oc[qq] & 0x40000000) ? 0.f : d6_relu(q[qq] + sh3[j]);
+        for (int qq = 0; qq < 4; ++qq) pend[j][qq] = d6_compact_is_empty(cur.oc[qq]) ? 0.f : d6_relu(q[qq] + sh3[j]);
         continue;
       }
 #pragma unroll
@@ -533,12 +521,9 @@ __global__ __launch_bounds__(512) void mlp_chain_wide_kernel(const ChainArgs g) 
   float *W2 = W1 + (K1 + 2) * C1;           // (C1 + 2) x C2
   float *W3 = W2 + (C1 + 2) * C2;           // C2 x C3
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, kh = lane >> 5;
-  // compact lists: the grid is sized for the capacity but the list holds a fraction of it: only the workgroups that get at
-  // least kPackTiles tiles per wave stay (the others leave before staging the 66-92 KB of weights); the live tiles are
-  // dealt round them, tile t -> wave t mod (active waves).
   int pk_stride = 0, pk_first = 0, pk_end = 0;
-  if (COMPACT) {   // tile t -> wave t mod (active waves): every workgroup sees the same mix of classes (see mlp_chain_reg_kernel)
-    const int wpw = blockDim.x >> 6, live = g.hdr[0] / 32;
+  if (COMPACT) {   // the workgroups that stay and the deal of the live tiles: as in mlp_chain_reg_kernel, see there
+    const int wpw = blockDim.x >> 6, live = g.hdr[kCompactHdrLive] / 32;
     int nb = (live + wpw * kPackTiles - 1) / (wpw * kPackTiles);
     if (nb > (int)gridDim.x) nb = gridDim.x;
     if ((int)blockIdx.x >= nb) return;
@@ -569,7 +554,7 @@ __global__ __launch_bounds__(512) void mlp_chain_wide_kernel(const ChainArgs g) 
   const int wave_global = COMPACT ? pk_first : (int)((blockIdx.x * blockDim.x + tid) >> 6);
   const int n_waves = COMPACT ? pk_stride : (int)((gridDim.x * blockDim.x) >> 6);   // tile stride of this wave
   int h1 = 0, h2 = 0, h3 = 0, h4 = 0, h5 = 0;
-  if (COMPACT) { h1 = g.hdr[1]; h2 = g.hdr[2]; h3 = g.hdr[3]; h4 = g.hdr[4]; h5 = g.hdr[5]; }
+  if (COMPACT) d6_compact_class_ends(g.hdr, h1, h2, h3, h4, h5);
   const int ntiles = COMPACT ? pk_end : g.rows / 32;                                 // end of this wave's tile range
   int tile = __builtin_amdgcn_readfirstlane(wave_global);
   if (tile >= ntiles) return;
@@ -599,18 +584,14 @@ __global__ __launch_bounds__(512) void mlp_chain_wide_kernel(const ChainArgs g) 
       xin[S1 - 2] = row[kh ? 0 : K1 - 1];       // ... then (pad, x) and (y, z): chain_col(64..67, 68) = 67, 0, 1, 2
       xin[S1 - 1] = row[kh ? 2 : 1];
       const int cj = e_c;
-      const float *c = g.ctr + (size_t)(cj < 0 ? 0 : cj & 0x1fffffff) * g.ldctr;
+      const float *c = g.ctr + (size_t)(cj < 0 ? 0 : cj & kCompactTagCentre) * g.ldctr;
       csub0 = kh ? c[0] : 0.f;
       csub1 = kh ? c[2] : c[1];
       cnt0 = cnt1 = 0;
       tag_n = cj;
-      const int sc = compact_class(t * 32, h1, h2, h3, h4, h5);
+      const int sc = d6_compact_class(t * 32, h1, h2, h3, h4, h5);
 #pragma unroll
-      for (int qq = 0; qq < 4; ++qq) {   // tags of the pooled rows from the lanes that hold them
-        const int r = compact_out_row(sc, qq, kh);
-        const int tg = __shfl(cj, r < 0 ? 0 : r);
-        oc_n[qq] = r >= 0 ? tg : -1;
-      }
+      for (int qq = 0; qq < 4; ++qq) oc_n[qq] = chain_pooled_tag(cj, sc, qq, kh);
       return;
     }
     const int c0 = NS == 32 ? t : 2 * t;
@@ -629,37 +610,10 @@ __global__ __launch_bounds__(512) void mlp_chain_wide_kernel(const ChainArgs g) 
     cnt0 = g.cnt[c0];
     cnt1 = NS == 32 ? 0 : g.cnt[c0 + 1];
   };
-  auto to_fragments = [&](const f32x16 &a, float *frag) {   // 16 accumulator registers -> 16 k-step fragments
-#pragma unroll
-    for (int G = 0; G < 4; ++G) {
-      float t[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) t[e] = d6_relu(a[4 * G + e]);
-      asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1\n\tv_permlane32_swap_b32 %2, %3\n\ts_nop 1"
-                   : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));
-      frag[4 * G + 0] = t[0]; frag[4 * G + 1] = t[2]; frag[4 * G + 2] = t[1]; frag[4 * G + 3] = t[3];
-    }
-  };
-
   float pend[T3][COMPACT ? 4 : 2];
   int pend_oc[4] = {-1, -1, -1, -1};
   int pend_tile = -1;
-  auto flush = [&]() {
-#pragma unroll
-    for (int j = 0; j < T3; ++j) {
-      const int col = 32 * j + l31;
-      if (COMPACT) {
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq)
-          if (pend_oc[qq] >= 0) compact_store(g.y + (size_t)(pend_oc[qq] & 0x1fffffff) * g.ldy + g.col0 + col, pend[j][qq], pend_oc[qq]);
-      } else if (NS == 32) {
-        g.y[(size_t)pend_tile * g.ldy + g.col0 + col] = pend[j][0];
-      } else {
-        g.y[(size_t)(2 * pend_tile) * g.ldy + g.col0 + col] = pend[j][0];
-        g.y[(size_t)(2 * pend_tile + 1) * g.ldy + g.col0 + col] = pend[j][1];
-      }
-    }
-  };
+  auto flush = [&]() { chain_flush<NS, COMPACT>(g, pend, pend_oc, pend_tile, l31); };   // bound here: a direct call compiles differently
 
   fetch_entries(tile);
   fetch(tile);
@@ -681,7 +635,7 @@ __global__ __launch_bounds__(512) void mlp_chain_wide_kernel(const ChainArgs g) 
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[e] = 0.f;
       mfma_steps_lds<S1 + 1, 2 * C1, true>(W1 + kh * C1 + 32 * t + l31, xin, acc);
-      to_fragments(acc, f1 + 16 * t);
+      chain_to_fragments(acc, f1 + 16 * t, 16);
     }
     f1[S2] = one_k0;
     // the input registers are free: start the next tile's gather now (its list entries arrived a tile ago), it lands
@@ -698,7 +652,7 @@ __global__ __launch_bounds__(512) void mlp_chain_wide_kernel(const ChainArgs g) 
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[e] = 0.f;
       mfma_steps_lds<S2 + 1, 2 * C2, true>(W2 + kh * C2 + 32 * t + l31, f1, acc);
-      to_fragments(acc, f2 + 16 * t);
+      chain_to_fragments(acc, f2 + 16 * t, 16);
     }
     // ---- layer 3 (rows in the registers): C2 -> C3, pool, shift, ReLU, mask ----
 #pragma unroll
@@ -711,18 +665,18 @@ __global__ __launch_bounds__(512) void mlp_chain_wide_kernel(const ChainArgs g) 
       if (COMPACT) {
 #pragma unroll
         for (int qq = 0; qq < 4; ++qq) q[qq] = d6_vmax(d6_vmax(o[4 * qq], o[4 * qq + 1]), d6_vmax(o[4 * qq + 2], o[4 * qq + 3]));
-        const int sc = compact_class(tile * 32, h1, h2, h3, h4, h5);
+        const int sc = d6_compact_class(tile * 32, h1, h2, h3, h4, h5);
         if (sc < 4) {
           int tags[16];
-          compact_row_tags(my_tag, kh, tags);
-          compact_store_small(g, o, sc, tags, 32 * j + l31, sh3[j]);
+          chain_row_tags(my_tag, kh, tags);
+          chain_store_small(g, o, sc, tags, 32 * j + l31, sh3[j]);
 #pragma unroll
           for (int qq = 0; qq < 4; ++qq) pend[j][qq] = 0.f;
           continue;
         }
-        compact_pool(q, sc);
+        d6_compact_pool(q, sc);
 #pragma unroll
-        for (int qq = 0; qq < 4; ++qq) pend[j][qq] = (my_oc[qq] & 0x40000000) ? 0.f : d6_relu(q[qq] + sh3[j]);
+        for (int qq = 0; qq < 4; ++qq) pend[j][qq] = d6_compact_is_empty(my_oc[qq]) ? 0.f : d6_relu(q[qq] + sh3[j]);
         continue;
       }
 #pragma unroll
@@ -749,6 +703,27 @@ __global__ __launch_bounds__(512) void mlp_chain_wide_kernel(const ChainArgs g) 
 
 }  // namespace
 
+// ---- host side ----
+
+// dense rows: idx / cnt and (n, m, ns), no list; compact rows: the list (hdr, crow_p, crow_c), rows = its capacity, the rest 0
+static ChainArgs chain_args(int rows, int n, int m, int ns, const float *a, int lda, const int *idx, const float *ctr, int ldctr,
+                            const int *cnt, const float *w1, int ldw1, const float *s1, int c1, const float *w2, int ldw2,
+                            const float *s2, int c2, const float *w3, int ldw3, const float *s3, int c3, float *y, int ldy,
+                            int col0, const int *hdr, const int *crow_p, const int *crow_c) {
+  return ChainArgs{rows, n, m, ns, a, lda, idx, ctr, ldctr, cnt, w1, w2, w3, ldw1, ldw2, ldw3, s1, s2, s3, /* k1 = */ lda, c1, c2, c3,
+                   y, ldy, col0, hdr, crow_p, crow_c};   // the struct's field order
+}
+
+// the wide kernel: one 512-thread workgroup per CU (the weights fill most of its LDS), two waves per SIMD
+template <int C2, int NS, bool COMPACT>
+static void launch_wide(const ChainArgs &g, hipStream_t stream) {
+  const size_t lds_bytes = sizeof(float) * ((size_t)70 * 64 + (size_t)66 * C2 + (size_t)C2 * 128);
+  const int ntiles = g.rows / 32;
+  const int wb = det6d_divup(ntiles, 8) < 256 ? det6d_divup(ntiles, 8) : 256;
+  DET6D_MAX_DYNAMIC_LDS((mlp_chain_wide_kernel<C2, NS, COMPACT>), lds_bytes);
+  hipLaunchKernelGGL((mlp_chain_wide_kernel<C2, NS, COMPACT>), dim3(wb), dim3(512), lds_bytes, stream, g);
+}
+
 DET6D_API int det6d_mlp_chain3(int rows, int n, int m, int ns, const float *a, int lda, const int *idx,
                                const float *ctr, int ldctr, const int *cnt, const float *w1, int ldw1,
                                const float *s1, int c1, const float *w2, int ldw2, const float *s2, int c2,
@@ -768,28 +743,14 @@ DET6D_API int det6d_mlp_chain3(int rows, int n, int m, int ns, const float *a, i
   }
   if (ldw1 < c1 || ldw2 < c2 || ldw3 < c3 || rows % (m * ns) || rows % 32) return DET6D_EINVAL;
   if (rows == 0) return DET6D_OK;
-  ChainArgs g;
-  g.rows = rows; g.n = n; g.m = m; g.ns = ns;
-  g.a = a; g.lda = lda; g.idx = idx; g.ctr = ctr; g.ldctr = ldctr; g.cnt = cnt;
-  g.w1 = w1; g.w2 = w2; g.w3 = w3; g.ldw1 = ldw1; g.ldw2 = ldw2; g.ldw3 = ldw3;
-  g.s1 = s1; g.s2 = s2; g.s3 = s3;
-  g.k1 = lda; g.c1 = c1; g.c2 = c2; g.c3 = c3;
-  g.y = y; g.ldy = ldy; g.col0 = col0;
-  g.hdr = nullptr; g.crow_p = nullptr; g.crow_c = nullptr;
+  const ChainArgs g = chain_args(rows, n, m, ns, a, lda, idx, ctr, ldctr, cnt, w1, ldw1, s1, c1, w2, ldw2, s2, c2, w3, ldw3, s3, c3, y,
+                                 ldy, col0, nullptr, nullptr, nullptr);
   const int ntiles = rows / 32;
-  if (wide) {   // one 512-thread workgroup per CU (weights fill most of its LDS), two waves per SIMD
-    const size_t lds_bytes = sizeof(float) * ((size_t)70 * 64 + (size_t)66 * c2 + (size_t)c2 * 128);
-    const int wb = det6d_divup(ntiles, 8) < 256 ? det6d_divup(ntiles, 8) : 256;
-#define D6_WIDE(C2V, NSV)                                                                                              \
-  do {                                                                                                                 \
-    DET6D_MAX_DYNAMIC_LDS((mlp_chain_wide_kernel<C2V, NSV>), lds_bytes);                                               \
-    hipLaunchKernelGGL((mlp_chain_wide_kernel<C2V, NSV>), dim3(wb), dim3(512), lds_bytes, (hipStream_t)stream, g);     \
-  } while (0)
-    if (c2 == 64 && ns == 16) D6_WIDE(64, 16);
-    else if (c2 == 64) D6_WIDE(64, 32);
-    else if (ns == 16) D6_WIDE(96, 16);
-    else D6_WIDE(96, 32);
-#undef D6_WIDE
+  if (wide) {
+    if (c2 == 64 && ns == 16) launch_wide<64, 16, false>(g, (hipStream_t)stream);
+    else if (c2 == 64) launch_wide<64, 32, false>(g, (hipStream_t)stream);
+    else if (ns == 16) launch_wide<96, 16, false>(g, (hipStream_t)stream);
+    else launch_wide<96, 32, false>(g, (hipStream_t)stream);
     return det6d_check_launch("det6d_mlp_chain3");
   }
   int blocks = det6d_divup(ntiles, kChainWaves);
@@ -828,25 +789,12 @@ DET6D_API int det6d_mlp_chain3_compact(int capacity, const int *hdr, const int *
                     !(((uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)w3 | (uintptr_t)s1 | (uintptr_t)s2) & 15);
   const bool narrow = lda == 4 && !((uintptr_t)a & 15) && ((c1 == 16 && c2 == 16 && c3 == 32) || (c1 == 32 && c2 == 32 && c3 == 64));
   if (!wide && !narrow) return DET6D_EINVAL;
-  ChainArgs g;
-  g.rows = capacity; g.n = 0; g.m = 0; g.ns = 0;
-  g.a = a; g.lda = lda; g.idx = nullptr; g.ctr = ctr; g.ldctr = ldctr; g.cnt = nullptr;
-  g.w1 = w1; g.w2 = w2; g.w3 = w3; g.ldw1 = ldw1; g.ldw2 = ldw2; g.ldw3 = ldw3;
-  g.s1 = s1; g.s2 = s2; g.s3 = s3;
-  g.k1 = lda; g.c1 = c1; g.c2 = c2; g.c3 = c3;
-  g.y = y; g.ldy = ldy; g.col0 = col0;
-  g.hdr = hdr; g.crow_p = crow_p; g.crow_c = crow_c;
+  const ChainArgs g = chain_args(capacity, 0, 0, 0, a, lda, nullptr, ctr, ldctr, nullptr, w1, ldw1, s1, c1, w2, ldw2, s2, c2, w3, ldw3,
+                                 s3, c3, y, ldy, col0, hdr, crow_p, crow_c);
   const int ntiles = capacity / 32;
   if (wide) {
-    const size_t lds_bytes = sizeof(float) * ((size_t)70 * 64 + (size_t)66 * c2 + (size_t)c2 * 128);
-    const int wb = det6d_divup(ntiles, 8) < 256 ? det6d_divup(ntiles, 8) : 256;
-    if (c2 == 64) {
-      DET6D_MAX_DYNAMIC_LDS((mlp_chain_wide_kernel<64, 32, true>), lds_bytes);
-      hipLaunchKernelGGL((mlp_chain_wide_kernel<64, 32, true>), dim3(wb), dim3(512), lds_bytes, (hipStream_t)stream, g);
-    } else {
-      DET6D_MAX_DYNAMIC_LDS((mlp_chain_wide_kernel<96, 32, true>), lds_bytes);
-      hipLaunchKernelGGL((mlp_chain_wide_kernel<96, 32, true>), dim3(wb), dim3(512), lds_bytes, (hipStream_t)stream, g);
-    }
+    if (c2 == 64) launch_wide<64, 32, true>(g, (hipStream_t)stream);
+    else launch_wide<96, 32, true>(g, (hipStream_t)stream);
     return det6d_check_launch("det6d_mlp_chain3_compact");
   }
   // grid: up to 2048 workgroups, each wave walks ceil(live tiles / waves) tiles (measured on 32-scene passes, SA1's wide

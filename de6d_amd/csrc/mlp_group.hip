@@ -20,6 +20,7 @@
 // Arithmetic: every output is the oracle's chain (features ascending, then dx, dy, dz for layer 1; k ascending for
 // layers 2, 3; + shift; ReLU; max over the rows of a centre) — bit-identical to the three-launch path.
 #include "common.h"
+#include "compact_list.h"
 
 namespace {
 
@@ -41,7 +42,7 @@ struct GroupArgs {
   float *y; int ldy; int col0;
   int pre;                                        // A/B switch: list entries of the next tile requested a K loop ahead
   int yvec;                                       // y rows are 16-byte aligned (ldy, col0 multiples of 4): vector stores allowed
-  int *ticket;                                    // compact rows: tile ticket + exit counter (hdr[10], hdr[11]); nullptr: static tiles
+  int *ticket;                                    // compact rows: tile ticket + exit counter (hdr + kCompactHdrTicket); nullptr: static tiles
 };
 
 // ---- tiles by ticket (round 5) --------------------------------------------------------------------------------------------
@@ -65,34 +66,6 @@ __device__ __forceinline__ void g_leave(int *ticket, int workers) {
   if (gone == workers - 1) {
     __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(ticket + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// ---- compact-row helpers (same conventions as mlp_chain.hip / linear.hip; see compact.hip for the list layout) ----
-__device__ __forceinline__ int g_class(int row0, int h1, int h2, int h3, int h4, int h5) {
-  return row0 < h1 ? 32 : row0 < h2 ? 16 : row0 < h3 ? 8 : row0 < h4 ? 4 : row0 < h5 ? 2 : 1;
-}
-__device__ __forceinline__ int g_out_row(int s, int qq, int kh) {
-  if (s < 4) return -1;
-  if (s == 4) return 8 * qq + 4 * kh;
-  if (kh) return -1;
-  if (s == 8) return 8 * qq;
-  if (s == 16) return (qq & 1) ? -1 : 8 * qq;
-  return qq == 0 ? 0 : -1;
-}
-__device__ __forceinline__ void g_store(float *dst, float val, int tag) {
-  if (tag & 0x20000000) __hip_atomic_fetch_max(reinterpret_cast<int *>(dst), __builtin_bit_cast(int, val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else *dst = val;
-}
-__device__ __forceinline__ void g_pool(float (&v)[4], int s) {
-  if (s == 4) return;
-#pragma unroll
-  for (int qq = 0; qq < 4; ++qq) v[qq] = d6_vmax(v[qq], __shfl_xor(v[qq], 32));
-  if (s == 16) {
-    v[0] = d6_vmax(v[0], v[1]);
-    v[2] = d6_vmax(v[2], v[3]);
-  } else if (s == 32) {
-    v[0] = d6_vmax(d6_vmax(v[0], v[1]), d6_vmax(v[2], v[3]));
   }
 }
 
@@ -124,15 +97,15 @@ __device__ __forceinline__ void g_store_group(float *rowptr, const float (&v)[VW
   const bool live = tag >= 0;
   const int l31 = lane & 31;
   if constexpr (VW == 1) {
-    if (live) g_store(rowptr + l31, v[0], tag);
+    if (live) d6_compact_store(rowptr + l31, v[0], tag);
   } else {
     if (!yvec) {
 #pragma unroll
       for (int t = 0; t < VW; ++t)
-        if (live) g_store(rowptr + VW * l31 + t, v[t], tag);
+        if (live) d6_compact_store(rowptr + VW * l31 + t, v[t], tag);
       return;
     }
-    const bool atomic = live && (tag & 0x20000000);
+    const bool atomic = live && (tag & kCompactTagSplit);
     typename BVec<VW>::T pack;
 #pragma unroll
     for (int t = 0; t < VW; ++t) pack[t] = v[t];
@@ -280,7 +253,7 @@ __device__ __forceinline__ void group_layer1(const GroupArgs &g, const int tile,
         const int tag = e0;
         if (eq == 0) tagbuf[erow] = tag;     // the pooling epilogue takes the rows' tags from LDS (visible after the barrier)
         real = tag >= 0;
-        cj = tag & 0x1fffffff;
+        cj = d6_compact_centre(tag);
         prow = e1;
       } else {
         cj = r / g.ns;
@@ -311,7 +284,7 @@ __device__ __forceinline__ void group_layer1(const GroupArgs &g, const int tile,
 }
 
 // ---- max-pool of the third layer's accumulators over the rows of a centre + shift + ReLU + store (compact rows: class
-// layout of compact.hip, parts of a centre combined with an atomic max; dense rows: nsample 32 / 16 per centre) ----
+// layout of compact_list.h, parts of a centre combined with an atomic max; dense rows: nsample 32 / 16 per centre) ----
 template <int TN3, bool COMPACT>
 __device__ __forceinline__ void group_pool_store(const GroupArgs &g, const int tile, f32x16 (&acc)[TN3], const float (&sh3)[TN3],
                                                  const int colbase, const int l31, const int kh, const int h1, const int h2,
@@ -321,13 +294,13 @@ __device__ __forceinline__ void group_pool_store(const GroupArgs &g, const int t
     constexpr int NG = TN3 / VW;                      // groups of 32 VW columns
     const int lane = l31 + 32 * kh;
     if (COMPACT) {
-      const int sc = g_class(tile * 32, h1, h2, h3, h4, h5);
+      const int sc = d6_compact_class(tile * 32, h1, h2, h3, h4, h5);
       if (sc < 4) {       // classes 1, 2: every accumulator (pair) is a centre part of its own
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           if (sc == 2 && (e & 1)) continue;
           const int tag = tagbuf[(e & 3) + 8 * (e >> 2) + 4 * kh];
-          float *dst = g.y + (size_t)(tag < 0 ? 0 : tag & 0x1fffffff) * g.ldy + g.col0 + colbase;
+          float *dst = g.y + (size_t)(tag < 0 ? 0 : tag & kCompactTagCentre) * g.ldy + g.col0 + colbase;
 #pragma unroll
           for (int jg = 0; jg < NG; ++jg) {
             float v[VW];
@@ -335,7 +308,7 @@ __device__ __forceinline__ void group_pool_store(const GroupArgs &g, const int t
             for (int t = 0; t < VW; ++t) {
               const int j = jg * VW + t;
               const float raw = sc == 2 ? d6_vmax(acc[j][e], acc[j][e + 1 < 16 ? e + 1 : e]) : acc[j][e];
-              v[t] = (tag & 0x40000000) ? 0.f : d6_relu(raw + sh3[j]);
+              v[t] = d6_compact_is_empty(tag) ? 0.f : d6_relu(raw + sh3[j]);
             }
             g_store_group<VW>(dst + jg * 32 * VW, v, tag, scr, lane, g.yvec);
           }
@@ -344,7 +317,7 @@ __device__ __forceinline__ void group_pool_store(const GroupArgs &g, const int t
         int oc[4];
 #pragma unroll
         for (int qq = 0; qq < 4; ++qq) {
-          const int rr = g_out_row(sc, qq, kh);
+          const int rr = d6_compact_out_row(sc, qq, kh);
           oc[qq] = rr >= 0 ? tagbuf[rr] : -1;
         }
 #pragma unroll
@@ -356,14 +329,14 @@ __device__ __forceinline__ void group_pool_store(const GroupArgs &g, const int t
 #pragma unroll
             for (int qq = 0; qq < 4; ++qq)
               q[t][qq] = d6_vmax(d6_vmax(acc[j][4 * qq], acc[j][4 * qq + 1]), d6_vmax(acc[j][4 * qq + 2], acc[j][4 * qq + 3]));
-            g_pool(q[t], sc);
+            d6_compact_pool(q[t], sc);
           }
 #pragma unroll
           for (int qq = 0; qq < 4; ++qq) {
             float v[VW];
 #pragma unroll
-            for (int t = 0; t < VW; ++t) v[t] = (oc[qq] & 0x40000000) ? 0.f : d6_relu(q[t][qq] + sh3[jg * VW + t]);
-            float *dst = g.y + (size_t)(oc[qq] < 0 ? 0 : oc[qq] & 0x1fffffff) * g.ldy + g.col0 + colbase + jg * 32 * VW;
+            for (int t = 0; t < VW; ++t) v[t] = d6_compact_is_empty(oc[qq]) ? 0.f : d6_relu(q[t][qq] + sh3[jg * VW + t]);
+            float *dst = g.y + (size_t)(oc[qq] < 0 ? 0 : oc[qq] & kCompactTagCentre) * g.ldy + g.col0 + colbase + jg * 32 * VW;
             g_store_group<VW>(dst, v, oc[qq], scr, lane, g.yvec);
           }
         }
@@ -414,10 +387,10 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && C3 <= 256) ? 3 : 1) void mlp_g
   int it = 0;                                                     // epilogue and the next tile's first layer)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, kh = lane >> 5;
   float *scr = reinterpret_cast<float *>(tags + 64) + wave * (64 * (TN3 >= 4 ? 4 : TN3));   // wave-private: g_store_group
-  const int live_tiles = (COMPACT ? g.hdr[0] : g.rows) / 32;
+  const int live_tiles = (COMPACT ? g.hdr[kCompactHdrLive] : g.rows) / 32;
   if ((int)blockIdx.x >= live_tiles) return;
   int h1 = 0, h2 = 0, h3 = 0, h4 = 0, h5 = 0;
-  if (COMPACT) { h1 = g.hdr[1]; h2 = g.hdr[2]; h3 = g.hdr[3]; h4 = g.hdr[4]; h5 = g.hdr[5]; }
+  if (COMPACT) d6_compact_class_ends(g.hdr, h1, h2, h3, h4, h5);
 
   const __amdgpu_buffer_rsrc_t srd2 = __builtin_amdgcn_make_buffer_rsrc((void *)g.w2, 0, 0xffffffff, 0x00020000);
   const __amdgpu_buffer_rsrc_t srd3 = __builtin_amdgcn_make_buffer_rsrc((void *)g.w3, 0, 0xffffffff, 0x00020000);
@@ -569,10 +542,10 @@ __global__ __launch_bounds__(256, 2) void mlp_group_stream_kernel(const GroupArg
   int it = 0;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, kh = lane >> 5;
   float *scr = reinterpret_cast<float *>(tags + 64) + wave * (64 * (TN3 >= 4 ? 4 : TN3));   // wave-private: g_store_group
-  const int live_tiles = (COMPACT ? g.hdr[0] : g.rows) / 32;
+  const int live_tiles = (COMPACT ? g.hdr[kCompactHdrLive] : g.rows) / 32;
   if ((int)blockIdx.x >= live_tiles) return;
   int h1 = 0, h2 = 0, h3 = 0, h4 = 0, h5 = 0;
-  if (COMPACT) { h1 = g.hdr[1]; h2 = g.hdr[2]; h3 = g.hdr[3]; h4 = g.hdr[4]; h5 = g.hdr[5]; }
+  if (COMPACT) d6_compact_class_ends(g.hdr, h1, h2, h3, h4, h5);
 
   const __amdgpu_buffer_rsrc_t srd2 = __builtin_amdgcn_make_buffer_rsrc((void *)g.w2, 0, 0xffffffff, 0x00020000);
   const __amdgpu_buffer_rsrc_t srd3 = __builtin_amdgcn_make_buffer_rsrc((void *)g.w3, 0, 0xffffffff, 0x00020000);
@@ -724,10 +697,10 @@ DET6D_API int det6d_mlp_group3(int rows, const float *p, int ldp, int pcol0, con
   g.pts = pts; g.ldpts = ldpts; g.ctr = ctr; g.ldctr = ldctr;
   g.idx = idx; g.n = n; g.m = m; g.ns = ns; g.cnt = cnt;
   g.hdr = hdr; g.crow_p = crow_p; g.crow_c = crow_c;
-  // tiles by ticket on compact lists (hdr[10], hdr[11]: zeroed by the list builder and by the kernels themselves); the
+  // tiles by ticket on compact lists (the header's ticket and exit words: zeroed by the list builder and by the kernels themselves); the
   // experiments build keeps the static walk behind DET6D_GROUP_STATIC=1 for A/B runs
   static const int static_tiles = det6d_env_int("DET6D_GROUP_STATIC", 0);
-  g.ticket = (hdr && !static_tiles) ? hdr + 10 : nullptr;
+  g.ticket = (hdr && !static_tiles) ? hdr + kCompactHdrTicket : nullptr;
   g.y = y; g.ldy = ldy; g.col0 = col0;
   static const int pre_entries = det6d_env_int("DET6D_GROUP_PRE", 1);
   g.pre = pre_entries;

@@ -134,12 +134,11 @@ def test_compact_groups_equals_c_oracle(oracle_ops, smin, split):
     np.testing.assert_array_equal(cr.crow_c.cpu().numpy()[:live], oc[:live])
 
 
-@pytest.mark.parametrize("kind", ["all_empty", "all_full", "all_single", "mixed_heavy_tail", "one_centre", "ragged_total"])
-def test_compact_groups_extreme_distributions(oracle_ops, kind):
-    """row lists on degenerate hit-count distributions == the C oracle's, and the MLP over them == the dense oracle"""
-    from de6d_amd.ops import fused
-    rng = np.random.default_rng(sum(map(ord, kind)))
-    b, n, ns = 2, 400, 32
+EXTREME_KINDS = ["all_empty", "all_full", "all_single", "mixed_heavy_tail", "one_centre", "ragged_total"]
+
+
+def extreme_query(rng, kind, b, n, ns):
+    """hit counts and padded index rows of a degenerate distribution: m, cnt (b, m), idx (b, m, ns)"""
     m = {"one_centre": 1, "ragged_total": 257}.get(kind, 300)
     cnt = {"all_empty": np.zeros((b, m)), "all_full": np.full((b, m), ns), "all_single": np.ones((b, m)),
            "mixed_heavy_tail": np.minimum(rng.zipf(1.5, (b, m)), ns), "one_centre": np.array([[5], [0]]),
@@ -150,6 +149,16 @@ def test_compact_groups_extreme_distributions(oracle_ops, kind):
             c = cnt[bi, j]
             if c:
                 idx[bi, j] = np.sort(rng.choice(n, c, replace=False))[np.arange(ns) % c]
+    return m, cnt, idx
+
+
+@pytest.mark.parametrize("kind", EXTREME_KINDS)
+def test_compact_groups_extreme_distributions(oracle_ops, kind):
+    """row lists on degenerate hit-count distributions == the C oracle's, and the MLP over them == the dense oracle"""
+    from de6d_amd.ops import fused
+    rng = np.random.default_rng(sum(map(ord, kind)))
+    b, n, ns = 2, 400, 32
+    m, cnt, idx = extreme_query(rng, kind, b, n, ns)
     for smin, split in ((1, 1), (4, 4)):
         cr = build_list(fused, cnt, idx, n, smin, split)
         ohdr, op, oc = oracle_ops.compact_groups(cnt, idx, n, smin=smin, split=split)
@@ -186,6 +195,30 @@ def make_layers(rng, ld, c_in, widths):
         layers_np.append((w, s))
         layers_dev.append((dev(w), dev(s), dims[i + 1], 1))
     return layers_np, layers_dev
+
+
+@pytest.mark.parametrize("widths", [(64, 64, 128), (64, 96, 128)])
+@pytest.mark.parametrize("kind", EXTREME_KINDS)
+def test_compact_wide_chain_extreme_distributions(oracle_ops, kind, widths):
+    """the wide chain kernel on the same degenerate lists == the dense oracle: a handful of live 32-row tiles (one_centre)
+    or whole classes missing, so the deal of the live tiles leaves workgroups, and waves of the last one, without a tile"""
+    from de6d_amd.ops import fused
+    rng = np.random.default_rng(sum(map(ord, kind)) + widths[1])
+    b, n, ns, c_in = 2, 400, 32, 64
+    m, cnt, idx = extreme_query(rng, kind, b, n, ns)
+    ld = (3 + c_in + 3) // 4 * 4
+    rows = np.zeros((b, n, ld), np.float32)
+    rows[..., :3 + c_in] = rng.normal(size=(b, n, 3 + c_in))
+    ctr = rng.normal(size=(b, m, 3)).astype(np.float32)
+    layers_np, layers_dev = make_layers(rng, ld, c_in, widths)
+    assert fused.chain_compact_eligible(ld, layers_dev)
+    out = torch.zeros((b * m, widths[2]), device="cuda")
+    cr = build_list(fused, cnt, idx, n, 1, 1)
+    fused.mlp_chain3_compact(dev(rows), cr, dev(ctr), layers_dev, out, 0)
+    h = oracle_ops.linear(rows, layers_np[0][0], layers_np[0][1], 1, idx=idx, ctr=ctr)
+    h = oracle_ops.linear(h, layers_np[1][0], layers_np[1][1], 1)
+    ref = oracle_ops.linear(h, layers_np[2][0], layers_np[2][1], 1, cnt=cnt, pool=ns)
+    np.testing.assert_array_equal(out.cpu().numpy(), ref)
 
 
 @pytest.mark.parametrize("c_in,widths,ns,chain", [(1, (16, 16, 32), 16, True), (1, (32, 32, 64), 32, True), (64, (64, 64, 128), 16, True),

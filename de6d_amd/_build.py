@@ -17,7 +17,7 @@ SOURCES = ["runtime.hip", "fps.hip", "fps_cells.hip", "fps_seq.hip", "fps_coop.h
 #: kernels that exist only in the -DDET6D_EXPERIMENTS library (measured alternatives that did not earn their place)
 EXPERIMENT_SOURCES = []
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "fps_common.h"), os.path.join(CSRC, "fps_multi.h"),
-           os.path.join(CSRC, "compact_list.h"),
+           os.path.join(CSRC, "compact_list.h"), os.path.join(CSRC, "mfma_tile.h"),
            os.path.join(HERE, "..", "include", "det6d_ops.h"),
            os.path.join(HERE, "..", "include", "det6d_math.h"),
            os.path.join(HERE, "..", "include", "det6d_geom.h"),

@@ -19,14 +19,12 @@
 // workgroups per CU hide each other's barriers.
 #include "common.h"
 #include "compact_list.h"
+#include "mfma_tile.h"
 #include <stdlib.h>
 
 namespace {
 
 D6_GEMM_PRIO_DECL
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 
 __device__ __forceinline__ float relu_act(float v, int act) { return act == 1 ? (v > 0.f ? v : 0.f) : v; }
 
@@ -35,8 +33,7 @@ __device__ __forceinline__ float relu_act(float v, int act) { return act == 1 ? 
 // BK = 32: 582 vs 539 us on 65536 x 512 x 1024; NBUF = 2: GEMM family 1.873 vs 1.840 ms.  Kept as knobs.
 // The bare LDS-fed MFMA loop (scripts/hiptests/lds_mfma.hip) reaches 138-155 TF depending on the box; the
 // largest layer runs at 123-129 TF in the model.
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
+//
 // FAST: the steady-state slabs are fetched with buffer_load_dwordx4 from per-thread byte offsets computed once
 // (rows / columns outside the problem are clamped to offset 0: they only feed outputs that are never stored)
 // plus a scalar k offset, so the main loop carries no address arithmetic, compares or zero-fill moves.
@@ -155,20 +152,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
     const bool ok = f < BK * B4_PER_ROW && c + 3 < g.ldw;
     voff_b[i] = ok ? (uint32_t)((f / B4_PER_ROW) * g.ldw + c) * 4u : 0u;
   }
-  const __amdgpu_buffer_rsrc_t srd_a = __builtin_amdgcn_make_buffer_rsrc((void *)g.a, 0, 0xffffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t srd_w = __builtin_amdgcn_make_buffer_rsrc((void *)g.w, 0, 0xffffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t srd_a = d6_buffer(g.a);
+  const __amdgpu_buffer_rsrc_t srd_w = d6_buffer(g.w);
   auto load_tile_fast = [&](int k0) {   // requires k0 > 0 and k0 + BK <= K
     const int soff_a = k0 * 4, soff_b = k0 * g.ldw * 4;
 #pragma unroll
     for (int i = 0; i < NA; ++i)
 #pragma unroll
       for (int u = 0; u < KU; ++u) {
-        const f32x4v v = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(srd_a, voff_a[i][u], soff_a, 0));
+        const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_a, voff_a[i][u], soff_a, 0));
         ra[i][u] = make_float4(v.x, v.y, v.z, v.w);
       }
 #pragma unroll
     for (int i = 0; i < NB4; ++i) {
-      const f32x4v v = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(srd_w, voff_b[i], soff_b, 0));
+      const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_w, voff_b[i], soff_b, 0));
       rb[i] = make_float4(v.x, v.y, v.z, v.w);
     }
   };
@@ -227,6 +224,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
     }
   };
 
+  // (local forms kept: d6_acc_zero here, d6_acc_max4 and d6_acc_row inside `rbase + .. + 4 * kh` below change the 128 x 128 kernels)
   f32x16 acc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
@@ -249,7 +247,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
     for (int i = 0; i < TM; ++i)
 #pragma unroll
       for (int j = 0; j < TN; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i], bf[j], acc[i][j], 0, 0, 0);
+        d6_mfma(af[i], bf[j], acc[i][j]);
   };
   auto compute = [&](int buf) {
     const float *As = As_all + buf * BK * LDA_S;
@@ -270,7 +268,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
         for (int i = 0; i < TM; ++i)
 #pragma unroll
           for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[ks & 1][i], bf[ks & 1][j], acc[i][j], 0, 0, 0);
+            d6_mfma(af[ks & 1][i], bf[ks & 1][j], acc[i][j]);
       }
       // issue order: the LDS reads of k-step s + 1 go out BEFORE the MFMAs of k-step s (left alone the scheduler puts them
       // behind, into the same registers, and every k-step waits out the LDS latency)
@@ -337,12 +335,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
     for (int i = 0; i < NA; ++i)
 #pragma unroll
       for (int u = 0; u < KU; ++u) {
-        const f32x4v v = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(srd_a, voff_a[i][u], soff0, 0));
+        const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_a, voff_a[i][u], soff0, 0));
         ra[i][u] = make_float4(v.x, v.y, v.z, v.w);
       }
 #pragma unroll
     for (int i = 0; i < NB4; ++i) {
-      const f32x4v v = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(srd_w, voff_b[i], soff0, 0));
+      const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_w, voff_b[i], soff0, 0));
       rb[i] = make_float4(v.x, v.y, v.z, v.w);
     }
     if (g.mode != DET6D_A_ROWS && akq == 0) {
@@ -434,7 +432,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
   // interior tiles of plain (non-pooled) layers: no bound predicates, no 64-bit address arithmetic — one
   // per-lane byte offset per 32x32 tile, the row of each accumulator register as a scalar offset
   if (FAST_EPI && g.pool == 0 && row0 + BM <= R && colb + BN <= N) {
-    const __amdgpu_buffer_rsrc_t srd_y = __builtin_amdgcn_make_buffer_rsrc((void *)g.y, 0, 0xffffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t srd_y = d6_buffer(g.y);
     const int ldy4 = g.ldy * 4;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -447,13 +445,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
         if (g.act == 1) {
 #pragma unroll
           for (int e = 0; e < 16; ++e)
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, d6_relu(acc[i][j][e] + sh)), srd_y, voff,
-                                                  ((e & 3) + 8 * (e >> 2)) * ldy4, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, d6_relu(acc[i][j][e] + sh)), srd_y, voff, d6_acc_row(e) * ldy4, 0);
         } else {
 #pragma unroll
           for (int e = 0; e < 16; ++e)
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, acc[i][j][e] + sh), srd_y, voff,
-                                                  ((e & 3) + 8 * (e >> 2)) * ldy4, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, acc[i][j][e] + sh), srd_y, voff, d6_acc_row(e) * ldy4, 0);
         }
       }
     }
@@ -463,7 +459,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
   // counts were fetched before the K loop, the lane^32 exchange is one v_permlane32_swap + one v_max, stores go
   // through the buffer path with the group row as a scalar offset, no bound predicates
   if (FAST_EPI && g.pool > 0 && row0 + BM <= R && colb + BN <= N) {
-    const __amdgpu_buffer_rsrc_t srd_y = __builtin_amdgcn_make_buffer_rsrc((void *)g.y, 0, 0xffffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t srd_y = d6_buffer(g.y);
     const int ldy4 = g.ldy * 4;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -474,13 +470,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
       for (int i = 0; i < TM; ++i) {
         float q[4];
 #pragma unroll
-        for (int qq = 0; qq < 4; ++qq) {
-          float lo = d6_vmax(d6_vmax(acc[i][j][4 * qq], acc[i][j][4 * qq + 1]), d6_vmax(acc[i][j][4 * qq + 2], acc[i][j][4 * qq + 3]));
-          float hi = lo;
-          // lo' = [lo.lanes0-31 | hi.lanes0-31], hi' = [lo.lanes32-63 | hi.lanes32-63]: max(lo', hi') is the 8-row maximum in BOTH halves
-          asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(lo), "+v"(hi));
-          q[qq] = d6_vmax(lo, hi);
-        }
+        for (int qq = 0; qq < 4; ++qq) q[qq] = d6_half_max_swap(d6_acc_max4(acc[i][j], qq));
         const int rbase = row0 + wm * 32 * TM + 32 * i;
         if (g.pool == 32) {
           const float m = relu_act(d6_vmax(d6_vmax(q[0], q[1]), d6_vmax(q[2], q[3])) + sh, g.act);
@@ -544,11 +534,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
           v[qq] = d6_vmax(d6_vmax(acc[i][j][4 * qq], acc[i][j][4 * qq + 1]), d6_vmax(acc[i][j][4 * qq + 2], acc[i][j][4 * qq + 3]));
         if (pool > 4) {
 #pragma unroll
-          for (int qq = 0; qq < 4; ++qq) {
-            float lo = v[qq], hi = v[qq];
-            asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(lo), "+v"(hi));
-            v[qq] = d6_vmax(lo, hi);
-          }
+          for (int qq = 0; qq < 4; ++qq) v[qq] = d6_half_max_swap(v[qq]);
           if (pool == 16) {
             v[0] = d6_vmax(v[0], v[1]);
             v[2] = d6_vmax(v[2], v[3]);
@@ -584,15 +570,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
           else if (col < g.ncols_pad && row < R) g.y[(size_t)row * g.ldy + g.col0 + col] = 0.f;   // padding columns of the next layer's K
         }
       } else {
-        // rows of a tile: (e&3) + 8*(e>>2) + 4*kh  -> 8-row bundle q = e>>2 spans both lane halves.
+        // rows of a tile (mfma_tile.h): the 8-row bundle q = e >> 2 spans both lane halves.
         // x -> act(x + shift) is monotone, so the max over the rows is taken on the raw accumulators and
         // shift / ReLU are applied to the pooled value only (identical result, a third of the vector ops).
         float q[4];
 #pragma unroll
-        for (int qq = 0; qq < 4; ++qq) {
-          float m = d6_vmax(d6_vmax(acc[i][j][4 * qq], acc[i][j][4 * qq + 1]), d6_vmax(acc[i][j][4 * qq + 2], acc[i][j][4 * qq + 3]));
-          q[qq] = d6_vmax(m, __shfl_xor(m, 32));
-        }
+        for (int qq = 0; qq < 4; ++qq)
+          q[qq] = d6_half_max(d6_vmax(d6_vmax(acc[i][j][4 * qq], acc[i][j][4 * qq + 1]), d6_vmax(acc[i][j][4 * qq + 2], acc[i][j][4 * qq + 3])));
         if (g.pool == 32) {
           const float m = relu_act(d6_vmax(d6_vmax(q[0], q[1]), d6_vmax(q[2], q[3])) + sh, g.act);
           const int grp = rbase / 32;

@@ -19,13 +19,12 @@
 // + shift, ReLU; masked max over the nsample rows.
 #include "common.h"
 #include "compact_list.h"
+#include "mfma_tile.h"
 #include <stdlib.h>
 
 namespace {
 
 D6_GEMM_PRIO_DECL
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kChainWaves = 4;
 constexpr int kPackTiles = 1;    // compact lists: tiles a wave must get before another workgroup is used (1: 9970, 2: 9910, 4: 9780 scenes/s)
@@ -69,7 +68,7 @@ __device__ __forceinline__ void chain_store_small(const ChainArgs &g, const f32x
 // than the others (the kernels' matrix pipes were busy 33-42 %: profiles/r03_beam_*).
 __device__ __forceinline__ void chain_row_tags(int my_tag, int kh, int (&tags)[16]) {
 #pragma unroll
-  for (int e = 0; e < 16; ++e) tags[e] = __shfl(my_tag, (e & 3) + 8 * (e >> 2) + 4 * kh);
+  for (int e = 0; e < 16; ++e) tags[e] = __shfl(my_tag, d6_acc_row(e) + 4 * kh);
 }
 // mlp_chain_kernel only: with d6_relu (common.h) in its place the compiler schedules that kernel differently (1118 -> 1241
 // lines of code), so the LDS kernel keeps the C form; the register kernels use d6_relu
@@ -140,57 +139,51 @@ __global__ __launch_bounds__(64 * kChainWaves) void mlp_chain_kernel(const Chain
       else { av[0] = t8[3]; av[1] = t8[4]; av[2] = t8[5]; av[3] = t8[6]; av[4] = t8[7]; av[5] = t8[0]; av[6] = t8[1]; av[7] = t8[2]; }
     }
     f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+    d6_acc_zero(acc);
 #pragma unroll
     for (int s = 0; s < kMaxK1 / 2; ++s) {
       if (2 * s < k1e) {
         const float a = kh ? av[2 * s + 1] : av[2 * s];
         const float b = W1[(2 * s + kh) * kMaxC + l31];
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+        d6_mfma(a, b, acc);
       }
     }
     {
       const float sh = S1[l31];
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int row = (e & 3) + 8 * (e >> 2) + 4 * kh;
+        const int row = d6_acc_row(e) + 4 * kh;
         T1[l31 * kTS + row] = relu1(acc[e] + sh);
       }
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_wave_barrier();
+    d6_lds_wave_sync();
     // ---- layer 2: K = c1 ----
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+    d6_acc_zero(acc);
     for (int s = 0; s < c1e / 2; ++s) {
       const float a = T1[(2 * s + kh) * kTS + l31];
       const float b = W2[(2 * s + kh) * kMaxC + l31];
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+      d6_mfma(a, b, acc);
     }
     {
       const float sh = S2[l31];
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int row = (e & 3) + 8 * (e >> 2) + 4 * kh;
+        const int row = d6_acc_row(e) + 4 * kh;
         T2[l31 * kTS + row] = relu1(acc[e] + sh);
       }
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_wave_barrier();
+    d6_lds_wave_sync();
     // ---- layer 3: K = c2, N = c3 (1 or 2 column tiles), then mask + max over the nsample rows ----
     f32x16 acc3[2];
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc3[j][e] = 0.f;
+    for (int j = 0; j < 2; ++j) d6_acc_zero(acc3[j]);
     for (int s = 0; s < c2e / 2; ++s) {
       const float a = T2[(2 * s + kh) * kTS + l31];
       const float b0 = W3[(2 * s + kh) * kMaxC3 + l31];
-      acc3[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b0, acc3[0], 0, 0, 0);
+      d6_mfma(a, b0, acc3[0]);
       if (nt3 > 1) {
         const float b1 = W3[(2 * s + kh) * kMaxC3 + 32 + l31];
-        acc3[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b1, acc3[1], 0, 0, 0);
+        d6_mfma(a, b1, acc3[1]);
       }
     }
 #pragma unroll
@@ -229,6 +222,7 @@ __global__ __launch_bounds__(64 * kChainWaves) void mlp_chain_kernel(const Chain
 }
 
 // ---- what the two register chain kernels share ----
+// (Not the per-column-tile pooling block, the same text in both: as ONE function it changed the wide kernel's code.)
 
 // tag of the row whose centre owns pooled value qq of this lane in a tile of class sc (-1: another lane writes it), from
 // the lane that loaded it: lane r holds the tag cj of row r, so the list is not read a second time.  (References on purpose:
@@ -401,36 +395,33 @@ __global__ __launch_bounds__(256) void mlp_chain_reg_kernel(const ChainArgs g) {
     const float cx = cur.cx, cy = cur.cy, cz = cur.cz;
     const float x0 = v0.x - cx, x1 = v0.y - cy, x2 = v0.z - cz, x3 = v0.w;
 
-    // ---- layer 1 (transposed): acc[e] = channel (e&3) + 8*(e>>2) + 4*kh of row l31 ----
+    // ---- layer 1 (transposed): acc[e] = channel d6_acc_row(e) + 4 * kh of row l31 ----
     f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf1[0], kh ? x0 : x3, acc, 0, 0, 0);   // chain order: f, dx, dy, dz
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf1[1], kh ? x2 : x1, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf1[2], one_k0, acc, 0, 0, 0);
+    d6_acc_zero(acc);
+    d6_mfma(wf1[0], kh ? x0 : x3, acc);   // chain order: f, dx, dy, dz
+    d6_mfma(wf1[1], kh ? x2 : x1, acc);
+    d6_mfma(wf1[2], one_k0, acc);
     float frag[16];   // frag[s] = activation fragment of k-step s: {half0: channel 2s, half1: channel 2s + 1}
     chain_to_fragments(acc, frag, S2);
     // ---- layer 2 (transposed) ----
+    d6_acc_zero(acc);
 #pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-    for (int s = 0; s < S2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf2[s], frag[s], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf2[S2], one_k0, acc, 0, 0, 0);
+    for (int s = 0; s < S2; ++s) d6_mfma(wf2[s], frag[s], acc);
+    d6_mfma(wf2[S2], one_k0, acc);
     chain_to_fragments(acc, frag, S3);
     // ---- layer 3 (rows in the registers again), shift + ReLU + mask + max over the nsample rows ----
 #pragma unroll
     for (int j = 0; j < NT3; ++j) {
       f32x16 o;
+      d6_acc_zero(o);
 #pragma unroll
-      for (int e = 0; e < 16; ++e) o[e] = 0.f;
-#pragma unroll
-      for (int s = 0; s < S3; ++s) o = __builtin_amdgcn_mfma_f32_32x32x2f32(frag[s], wf3[j][s], o, 0, 0, 0);
+      for (int s = 0; s < S3; ++s) d6_mfma(frag[s], wf3[j][s], o);
       const int col = 32 * j + l31;
       // max over the rows on the raw accumulators, shift + ReLU on the pooled value (monotone: same result)
       float q[4];
       if (COMPACT) {
 #pragma unroll
-        for (int qq = 0; qq < 4; ++qq) q[qq] = d6_vmax(d6_vmax(o[4 * qq], o[4 * qq + 1]), d6_vmax(o[4 * qq + 2], o[4 * qq + 3]));
+        for (int qq = 0; qq < 4; ++qq) q[qq] = d6_acc_max4(o, qq);
         const int sc = d6_compact_class(tile * 32, h1, h2, h3, h4, h5);
         if (sc < 4) {
           int tags[16];
@@ -446,10 +437,7 @@ __global__ __launch_bounds__(256) void mlp_chain_reg_kernel(const ChainArgs g) {
         continue;
       }
 #pragma unroll
-      for (int qq = 0; qq < 4; ++qq) {
-        const float mq = d6_vmax(d6_vmax(o[4 * qq], o[4 * qq + 1]), d6_vmax(o[4 * qq + 2], o[4 * qq + 3]));
-        q[qq] = d6_vmax(mq, __shfl_xor(mq, 32));
-      }
+      for (int qq = 0; qq < 4; ++qq) q[qq] = d6_half_max(d6_acc_max4(o, qq));
       if (NS == 32) {
         const float mx = d6_relu(d6_vmax(d6_vmax(q[0], q[1]), d6_vmax(q[2], q[3])) + sh3[j]);
         pend[j][0] = (cur.cnt0 > 0) ? mx : 0.f;   // both lane halves hold the pooled value: all 64 lanes store it
@@ -493,8 +481,8 @@ __device__ __forceinline__ void mfma_steps_lds(const float *__restrict__ w, cons
 #pragma unroll
     for (int u = 0; u < UB; ++u) {
       if (b * UB + u < N) {
-        if (W_IS_A) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[b & 1][u], x[b * UB + u], acc, 0, 0, 0);
-        else acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x[b * UB + u], wb[b & 1][u], acc, 0, 0, 0);
+        if (W_IS_A) d6_mfma(wb[b & 1][u], x[b * UB + u], acc);
+        else d6_mfma(x[b * UB + u], wb[b & 1][u], acc);
       }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -632,8 +620,7 @@ __global__ __launch_bounds__(512) void mlp_chain_wide_kernel(const ChainArgs g) 
 #pragma unroll
     for (int t = 0; t < T1; ++t) {
       f32x16 acc;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+      d6_acc_zero(acc);
       mfma_steps_lds<S1 + 1, 2 * C1, true>(W1 + kh * C1 + 32 * t + l31, xin, acc);
       chain_to_fragments(acc, f1 + 16 * t, 16);
     }
@@ -649,8 +636,7 @@ __global__ __launch_bounds__(512) void mlp_chain_wide_kernel(const ChainArgs g) 
 #pragma unroll
     for (int t = 0; t < T2; ++t) {
       f32x16 acc;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+      d6_acc_zero(acc);
       mfma_steps_lds<S2 + 1, 2 * C2, true>(W2 + kh * C2 + 32 * t + l31, f1, acc);
       chain_to_fragments(acc, f2 + 16 * t, 16);
     }
@@ -658,13 +644,12 @@ __global__ __launch_bounds__(512) void mlp_chain_wide_kernel(const ChainArgs g) 
 #pragma unroll
     for (int j = 0; j < T3; ++j) {
       f32x16 o;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) o[e] = 0.f;
+      d6_acc_zero(o);
       mfma_steps_lds<S3, 2 * C3, false>(W3 + kh * C3 + 32 * j + l31, f2, o);
       float q[4];
       if (COMPACT) {
 #pragma unroll
-        for (int qq = 0; qq < 4; ++qq) q[qq] = d6_vmax(d6_vmax(o[4 * qq], o[4 * qq + 1]), d6_vmax(o[4 * qq + 2], o[4 * qq + 3]));
+        for (int qq = 0; qq < 4; ++qq) q[qq] = d6_acc_max4(o, qq);
         const int sc = d6_compact_class(tile * 32, h1, h2, h3, h4, h5);
         if (sc < 4) {
           int tags[16];
@@ -680,10 +665,7 @@ __global__ __launch_bounds__(512) void mlp_chain_wide_kernel(const ChainArgs g) 
         continue;
       }
 #pragma unroll
-      for (int qq = 0; qq < 4; ++qq) {
-        const float mq = d6_vmax(d6_vmax(o[4 * qq], o[4 * qq + 1]), d6_vmax(o[4 * qq + 2], o[4 * qq + 3]));
-        q[qq] = d6_vmax(mq, __shfl_xor(mq, 32));
-      }
+      for (int qq = 0; qq < 4; ++qq) q[qq] = d6_half_max(d6_acc_max4(o, qq));
       if (NS == 32) {
         const float mx = d6_relu(d6_vmax(d6_vmax(q[0], q[1]), d6_vmax(q[2], q[3])) + sh3[j]);
         pend[j][0] = my_cnt0 > 0 ? mx : 0.f;

@@ -21,13 +21,12 @@
 // layers 2, 3; + shift; ReLU; max over the rows of a centre) — bit-identical to the three-launch path.
 #include "common.h"
 #include "compact_list.h"
+#include "mfma_tile.h"
 
 namespace {
 
 D6_GEMM_PRIO_DECL
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4g __attribute__((ext_vector_type(4)));
 
 struct GroupArgs {
   int rows;                                       // dense: b * m * ns; compact: capacity of the row list
@@ -56,7 +55,7 @@ struct GroupArgs {
 // (exit counter == workgroups that had a tile) zeroes both, so a launch may be replayed without rebuilding the list
 // (bench: family_saturated); compact_place_kernel zeroes them too when it builds the list.  Results do not depend on which
 // workgroup computes a tile (a tile's outputs are a function of its rows; multi-part centres combine by an order-independent
-// integer max).
+// integer max).  (Draw, publish by parity, read, leave stay spelled out in both kernels: as ONE walk object they changed them.)
 __device__ __forceinline__ int g_draw_ticket(int *ticket, int grid) {
   return grid + __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -72,16 +71,17 @@ __device__ __forceinline__ void g_leave(int *ticket, int workers) {
 // Column owned by (accumulator tile j, lane l31) inside a wave's C/4-wide quarter: VW = min(TN, 4) consecutive columns
 // per lane so that ONE buffer_load_dwordx{VW} brings the B operands of VW tiles (any assignment of columns to
 // (tile, lane) is a valid GEMM; the epilogues use the same map).
+template <int TN> constexpr int kGroupVW = TN >= 4 ? 4 : TN;
 template <int TN>
 __device__ __forceinline__ int tile_col(int j, int l31) {
-  constexpr int VW = TN >= 4 ? 4 : TN;
+  constexpr int VW = kGroupVW<TN>;
   return (j / VW) * (32 * VW) + VW * l31 + (j % VW);
 }
 
 template <int VW> struct BVec;
 template <> struct BVec<1> { typedef float T; };
-template <> struct BVec<2> { typedef float T __attribute__((ext_vector_type(2))); };
-template <> struct BVec<4> { typedef float T __attribute__((ext_vector_type(4))); };
+template <> struct BVec<2> { typedef f32x2 T; };
+template <> struct BVec<4> { typedef f32x4 T; };
 
 // Stores / max-combines the VW values a lane holds for ONE pooled row: VW CONSECUTIVE columns (4 l31 + t inside a group of
 // 32 VW columns: the column map of tile_col, which follows from the 16-byte B-fragment loads).
@@ -112,14 +112,12 @@ __device__ __forceinline__ void g_store_group(float *rowptr, const float (&v)[VW
     if (live && !atomic) *reinterpret_cast<typename BVec<VW>::T *>(rowptr + VW * l31) = pack;
     if (__ballot(atomic) != 0ull) {                       // wave-uniform
       *reinterpret_cast<typename BVec<VW>::T *>(scr + lane * VW) = pack;
-      __builtin_amdgcn_s_waitcnt(0xC07F);
-      __builtin_amdgcn_wave_barrier();
+      d6_lds_wave_sync();
       const float *half = scr + (lane & 32) * VW;         // this half's 32 VW values, column order
       float x[VW];
 #pragma unroll
       for (int t = 0; t < VW; ++t) x[t] = half[32 * t + l31];
-      __builtin_amdgcn_s_waitcnt(0xC07F);
-      __builtin_amdgcn_wave_barrier();                    // the scratch may be rewritten by the next call
+      d6_lds_wave_sync();                                 // the scratch may be rewritten by the next call
       if (atomic) {
 #pragma unroll
         for (int t = 0; t < VW; ++t)
@@ -171,7 +169,7 @@ __device__ unsigned long long d6_group_phase[8 + 18];   // [8] shader-clock cycl
 
 template <int K, int TN, int LDX>
 struct GroupLayer {
-  static constexpr int VW = TN >= 4 ? 4 : TN;
+  static constexpr int VW = kGroupVW<TN>;
   static constexpr int NV = TN / VW;         // loads per k-step
   static constexpr int KS = K / 2;           // k-steps of two
   static constexpr int UK = 32 / TN;         // k-steps per block
@@ -196,7 +194,7 @@ struct GroupLayer {
 #pragma unroll
     for (int u = 0; u < UK; ++u)
 #pragma unroll
-      for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], bget<VW>(b[u][j / VW], j % VW), acc[j], 0, 0, 0);
+      for (int j = 0; j < TN; ++j) d6_mfma(a[u], bget<VW>(b[u][j / VW], j % VW), acc[j]);
   }
   // the first two blocks of weights: issued BEFORE the phase that produces the layer's input (the first layer's gather,
   // the second layer's epilogue and the barrier behind it), so that the K loop does not start with an L2 round trip
@@ -269,11 +267,11 @@ __device__ __forceinline__ void group_layer1(const GroupArgs &g, const int tile,
       float *xr = X1 + erow * LD1;
 #pragma unroll 4
       for (int c = 4 * eq; c < C1; c += 4 * EPR) {
-        const f32x4g pv = *reinterpret_cast<const f32x4g *>(prow_p + c);
-        const f32x4g wx = *reinterpret_cast<const f32x4g *>(g.w1 + c);
-        const f32x4g wy = *reinterpret_cast<const f32x4g *>(g.w1 + g.ldw1 + c);
-        const f32x4g wz = *reinterpret_cast<const f32x4g *>(g.w1 + 2 * g.ldw1 + c);
-        const f32x4g sh = *reinterpret_cast<const f32x4g *>(g.s1 + c);
+        const f32x4 pv = *reinterpret_cast<const f32x4 *>(prow_p + c);
+        const f32x4 wx = *reinterpret_cast<const f32x4 *>(g.w1 + c);
+        const f32x4 wy = *reinterpret_cast<const f32x4 *>(g.w1 + g.ldw1 + c);
+        const f32x4 wz = *reinterpret_cast<const f32x4 *>(g.w1 + 2 * g.ldw1 + c);
+        const f32x4 sh = *reinterpret_cast<const f32x4 *>(g.s1 + c);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float v = d6_relu(D6_FMA(dz, wz[e], D6_FMA(dy, wy[e], D6_FMA(dx, wx[e], pv[e]))) + sh[e]);
@@ -290,7 +288,7 @@ __device__ __forceinline__ void group_pool_store(const GroupArgs &g, const int t
                                                  const int colbase, const int l31, const int kh, const int h1, const int h2,
                                                  const int h3, const int h4, const int h5, const int *__restrict__ tagbuf,
                                                  float *__restrict__ scr) {
-    constexpr int VW = TN3 >= 4 ? 4 : TN3;            // consecutive columns per lane (tile_col)
+    constexpr int VW = kGroupVW<TN3>;                 // consecutive columns per lane (tile_col)
     constexpr int NG = TN3 / VW;                      // groups of 32 VW columns
     const int lane = l31 + 32 * kh;
     if (COMPACT) {
@@ -299,7 +297,7 @@ __device__ __forceinline__ void group_pool_store(const GroupArgs &g, const int t
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           if (sc == 2 && (e & 1)) continue;
-          const int tag = tagbuf[(e & 3) + 8 * (e >> 2) + 4 * kh];
+          const int tag = tagbuf[d6_acc_row(e) + 4 * kh];
           float *dst = g.y + (size_t)(tag < 0 ? 0 : tag & kCompactTagCentre) * g.ldy + g.col0 + colbase;
 #pragma unroll
           for (int jg = 0; jg < NG; ++jg) {
@@ -328,7 +326,7 @@ __device__ __forceinline__ void group_pool_store(const GroupArgs &g, const int t
             const int j = jg * VW + t;
 #pragma unroll
             for (int qq = 0; qq < 4; ++qq)
-              q[t][qq] = d6_vmax(d6_vmax(acc[j][4 * qq], acc[j][4 * qq + 1]), d6_vmax(acc[j][4 * qq + 2], acc[j][4 * qq + 3]));
+              q[t][qq] = d6_acc_max4(acc[j], qq);
             d6_compact_pool(q[t], sc);
           }
 #pragma unroll
@@ -354,10 +352,7 @@ __device__ __forceinline__ void group_pool_store(const GroupArgs &g, const int t
           const int j = jg * VW + t;
           float q[4];
 #pragma unroll
-          for (int qq = 0; qq < 4; ++qq) {
-            const float mq = d6_vmax(d6_vmax(acc[j][4 * qq], acc[j][4 * qq + 1]), d6_vmax(acc[j][4 * qq + 2], acc[j][4 * qq + 3]));
-            q[qq] = d6_vmax(mq, __shfl_xor(mq, 32));
-          }
+          for (int qq = 0; qq < 4; ++qq) q[qq] = d6_half_max(d6_acc_max4(acc[j], qq));
           if (g.ns == 32) {
             const float mx = d6_relu(d6_vmax(d6_vmax(q[0], q[1]), d6_vmax(q[2], q[3])) + sh3[j]);
             v0[t] = cnt0 > 0 ? mx : 0.f;
@@ -386,14 +381,14 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && C3 <= 256) ? 3 : 1) void mlp_g
   int *tags = reinterpret_cast<int *>(lds + 32 * (LD1 + LD2));    // 2 x 32 row tags, by tile parity (no barrier between a tile's
   int it = 0;                                                     // epilogue and the next tile's first layer)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, kh = lane >> 5;
-  float *scr = reinterpret_cast<float *>(tags + 64) + wave * (64 * (TN3 >= 4 ? 4 : TN3));   // wave-private: g_store_group
+  float *scr = reinterpret_cast<float *>(tags + 64) + wave * (64 * kGroupVW<TN3>);   // wave-private: g_store_group
   const int live_tiles = (COMPACT ? g.hdr[kCompactHdrLive] : g.rows) / 32;
   if ((int)blockIdx.x >= live_tiles) return;
   int h1 = 0, h2 = 0, h3 = 0, h4 = 0, h5 = 0;
   if (COMPACT) d6_compact_class_ends(g.hdr, h1, h2, h3, h4, h5);
 
-  const __amdgpu_buffer_rsrc_t srd2 = __builtin_amdgcn_make_buffer_rsrc((void *)g.w2, 0, 0xffffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t srd3 = __builtin_amdgcn_make_buffer_rsrc((void *)g.w3, 0, 0xffffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t srd2 = d6_buffer(g.w2);
+  const __amdgpu_buffer_rsrc_t srd3 = d6_buffer(g.w3);
   const uint32_t voff2 = (uint32_t)(kh * g.ldw2 + wave * (C2 / NW) + tile_col<TN2>(0, l31)) * 4u;
   const uint32_t voff3 = (uint32_t)(kh * g.ldw3 + wave * (C3 / NW) + tile_col<TN3>(0, l31)) * 4u;
   float sh2[TN2], sh3[TN3];
@@ -428,9 +423,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && C3 <= 256) ? 3 : 1) void mlp_g
     {
       f32x16 acc[TN2];
 #pragma unroll
-      for (int j = 0; j < TN2; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
+      for (int j = 0; j < TN2; ++j) d6_acc_zero(acc[j]);
       D6_WAVE_T0;
       second.run(X1, srd2, voff2, g.ldw2 * 4, acc, l31, kh);
       third.start(srd3, voff3, g.ldw3 * 4);
@@ -440,7 +433,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && C3 <= 256) ? 3 : 1) void mlp_g
       for (int j = 0; j < TN2; ++j) {
         float *xc = X2 + wave * (C2 / NW) + tile_col<TN2>(j, l31);
 #pragma unroll
-        for (int e = 0; e < 16; ++e) xc[((e & 3) + 8 * (e >> 2) + 4 * kh) * LD2] = d6_relu(acc[j][e] + sh2[j]);
+        for (int e = 0; e < 16; ++e) xc[(d6_acc_row(e) + 4 * kh) * LD2] = d6_relu(acc[j][e] + sh2[j]);
       }
     }
     __syncthreads();
@@ -448,9 +441,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && C3 <= 256) ? 3 : 1) void mlp_g
     // ---- layer 3 + pooling ----
     f32x16 acc[TN3];
 #pragma unroll
-    for (int j = 0; j < TN3; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
+    for (int j = 0; j < TN3; ++j) d6_acc_zero(acc[j]);
     D6_WAVE_T0;
     if (g.pre) {          // the next tile's list entries, a K loop ahead of its first layer (the last tile re-reads its own)
       const int nt = next_tile;
@@ -485,7 +476,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && C3 <= 256) ? 3 : 1) void mlp_g
 template <int K, int TN, int LDX, int UK, int DEPTH>
 __device__ __forceinline__ void stream_layer(const float *__restrict__ X, const __amdgpu_buffer_rsrc_t srd, const uint32_t voff,
                                              const int ldw_bytes, const int soff0, f32x16 (&acc)[TN], const int l31, const int kh) {
-  constexpr int VW = TN >= 4 ? 4 : TN;
+  constexpr int VW = kGroupVW<TN>;
   constexpr int NV = TN / VW;
   constexpr int KS = K / 2;
   constexpr int NB = KS / UK;
@@ -519,7 +510,7 @@ __device__ __forceinline__ void stream_layer(const float *__restrict__ X, const 
 #pragma unroll
       for (int u = 0; u < UK; ++u)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], bget<VW>(b[d][u][j / VW], j % VW), acc[j], 0, 0, 0);
+        for (int j = 0; j < TN; ++j) d6_mfma(a[u], bget<VW>(b[d][u][j / VW], j % VW), acc[j]);
 #pragma unroll
       for (int u = 0; u < UK; ++u) a[u] = an[u];
     }
@@ -541,14 +532,14 @@ __global__ __launch_bounds__(256, 2) void mlp_group_stream_kernel(const GroupArg
   int *tags = reinterpret_cast<int *>(Y1 + 32 * LDY);             // 2 x 32 row tags, by tile parity
   int it = 0;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, kh = lane >> 5;
-  float *scr = reinterpret_cast<float *>(tags + 64) + wave * (64 * (TN3 >= 4 ? 4 : TN3));   // wave-private: g_store_group
+  float *scr = reinterpret_cast<float *>(tags + 64) + wave * (64 * kGroupVW<TN3>);   // wave-private: g_store_group
   const int live_tiles = (COMPACT ? g.hdr[kCompactHdrLive] : g.rows) / 32;
   if ((int)blockIdx.x >= live_tiles) return;
   int h1 = 0, h2 = 0, h3 = 0, h4 = 0, h5 = 0;
   if (COMPACT) d6_compact_class_ends(g.hdr, h1, h2, h3, h4, h5);
 
-  const __amdgpu_buffer_rsrc_t srd2 = __builtin_amdgcn_make_buffer_rsrc((void *)g.w2, 0, 0xffffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t srd3 = __builtin_amdgcn_make_buffer_rsrc((void *)g.w3, 0, 0xffffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t srd2 = d6_buffer(g.w2);
+  const __amdgpu_buffer_rsrc_t srd3 = d6_buffer(g.w3);
   const uint32_t voff2 = (uint32_t)(kh * g.ldw2 + 32 * wave + l31) * 4u;                          // + 128 c columns per chunk
   const uint32_t voff3 = (uint32_t)(kh * g.ldw3 + wave * (C3 / 4) + tile_col<TN3>(0, l31)) * 4u;   // + 128 c rows per chunk
   float sh3[TN3];
@@ -559,12 +550,11 @@ __global__ __launch_bounds__(256, 2) void mlp_group_stream_kernel(const GroupArg
   auto second = [&](const int c, float *__restrict__ Y) {
     const float sh2 = g.s2[CH * c + 32 * wave + l31];
     f32x16 acc2[1];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc2[0][e] = 0.f;
+    d6_acc_zero(acc2[0]);
     stream_layer<C1, 1, LD1, 8, 4>(X1, srd2, voff2, g.ldw2 * 4, CH * c * 4, acc2, l31, kh);
     float *yc = Y + 32 * wave + l31;
 #pragma unroll
-    for (int e = 0; e < 16; ++e) yc[((e & 3) + 8 * (e >> 2) + 4 * kh) * LDY] = d6_relu(acc2[0][e] + sh2);
+    for (int e = 0; e < 16; ++e) yc[(d6_acc_row(e) + 4 * kh) * LDY] = d6_relu(acc2[0][e] + sh2);
   };
 
   __shared__ int next_tile_s[2];
@@ -582,9 +572,7 @@ __global__ __launch_bounds__(256, 2) void mlp_group_stream_kernel(const GroupArg
     const int next_tile = ticket ? next_tile_s[par] : tile + (int)gridDim.x;
     f32x16 acc[TN3];
 #pragma unroll
-    for (int j = 0; j < TN3; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
+    for (int j = 0; j < TN3; ++j) d6_acc_zero(acc[j]);
     second(0, Y0);
     __syncthreads();
 #pragma unroll 1
@@ -606,33 +594,29 @@ __global__ __launch_bounds__(256, 2) void mlp_group_stream_kernel(const GroupArg
   if (ticket && tid == 0) g_leave(ticket, min((int)gridDim.x, live_tiles));
 }
 
+// persistent grid: as many workgroups as the chip holds at a time by their LDS (256 CUs x at most max_per_cu), one 32-row
+// tile each at the least
+static int group_grid(int rows, size_t lds_bytes, int max_per_cu) {
+  int per_cu = (int)((160 * 1024) / lds_bytes);
+  per_cu = per_cu < 1 ? 1 : (per_cu > max_per_cu ? max_per_cu : per_cu);
+  const int blocks = rows / 32;
+  return blocks > 256 * per_cu ? 256 * per_cu : blocks;
+}
+
 template <int C1, int C2, int C3, bool COMPACT>
 int launch_group_stream(const GroupArgs &g, hipStream_t stream) {
-  constexpr int kVW3 = (C3 / 128) >= 4 ? 4 : (C3 / 128);
-  const size_t lds_bytes = sizeof(float) * (32 * (size_t)(C1 + 1 + 2 * 129) + 64 + 4 * 64 * kVW3);   // + tags + store scratch
+  const size_t lds_bytes = sizeof(float) * (32 * (size_t)(C1 + 1 + 2 * 129) + 64 + 4 * 64 * kGroupVW<C3 / 128>);   // + tags + store scratch
   DET6D_MAX_DYNAMIC_LDS((mlp_group_stream_kernel<C1, C2, C3, COMPACT>), lds_bytes);
-  int per_cu = (int)((160 * 1024) / lds_bytes);      // 2 for the head's groups (66 KB), 3 for SA3's (52 KB)
-  per_cu = per_cu < 1 ? 1 : (per_cu > 3 ? 3 : per_cu);
-  int blocks = g.rows / 32;
-  if (blocks > 256 * per_cu) blocks = 256 * per_cu;
+  const int blocks = group_grid(g.rows, lds_bytes, 3);      // 2 per CU for the head's groups (66 KB), 3 for SA3's (52 KB)
   hipLaunchKernelGGL((mlp_group_stream_kernel<C1, C2, C3, COMPACT>), dim3(blocks), dim3(256), lds_bytes, stream, g);
   return det6d_check_launch("det6d_mlp_group3 (streaming)");
 }
 
 template <int C1, int C2, int C3, bool COMPACT, int NW>
 int launch_group(const GroupArgs &g, hipStream_t stream) {
-  constexpr int kTN3 = C3 / (32 * NW);
-  const size_t lds_bytes = sizeof(float) * (32 * (size_t)(C1 + 1 + C2 + 1) + 64 + NW * 64 * (kTN3 >= 4 ? 4 : kTN3));   // + tags + store scratch
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void *)mlp_group_kernel<C1, C2, C3, COMPACT, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    attr_set = true;
-  }
-  int per_cu = (int)((160 * 1024) / lds_bytes);
-  if (per_cu > 4) per_cu = 4;
-  if (per_cu < 1) per_cu = 1;
-  int blocks = g.rows / 32;
-  if (blocks > 256 * per_cu) blocks = 256 * per_cu;
+  const size_t lds_bytes = sizeof(float) * (32 * (size_t)(C1 + 1 + C2 + 1) + 64 + NW * 64 * kGroupVW<C3 / (32 * NW)>);   // + tags + store scratch
+  DET6D_MAX_DYNAMIC_LDS((mlp_group_kernel<C1, C2, C3, COMPACT, NW>), lds_bytes);
+  const int blocks = group_grid(g.rows, lds_bytes, 4);
 #ifdef DET6D_EXPERIMENTS
   static bool phase_set = false;
   if (!phase_set) {

@@ -8,13 +8,12 @@
 // input — the scheme of mlp_group.hip at run-time widths.
 // Every output is the same ascending-k fma chain as det6d_linear (+ shift, activation): bit-identical.
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
 D6_GEMM_PRIO_DECL
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4r __attribute__((ext_vector_type(4)));
 
 constexpr int kMaxLayers = 4;
 
@@ -48,26 +47,21 @@ __device__ __forceinline__ void rows_epilogue(f32x16 &acc, const det6d_rows_laye
   }
   if (Y != nullptr && cok) {
     float *yw = Y + (rb_row0 + 4 * kh) * LDY + col;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) yw[((e & 3) + 8 * (e >> 2)) * LDY] = acc[e];
+    d6_acc_to_lds(acc, yw, LDY);
   }
   if (L.out == nullptr) return;
   const int c0 = col & ~31;
   const bool interior = fits32 && row_g0 + rb_row0 + 32 <= rows && c0 + 32 <= L.n;      // wave-uniform
   if (interior) {
-    const __amdgpu_buffer_rsrc_t srd = __builtin_amdgcn_make_buffer_rsrc((void *)(L.out + L.ocol0), 0, 0xffffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t srd = d6_buffer(L.out + L.ocol0);
     const int ldo4 = L.ldo * 4;
     const uint32_t voff = (uint32_t)(row_g0 + rb_row0 + 4 * kh) * (uint32_t)ldo4 + (uint32_t)col * 4u;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const float v = acc[e];
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), srd, voff, ((e & 3) + 8 * (e >> 2)) * ldo4, 0);
-    }
+    d6_acc_store_rows(acc, srd, voff, ldo4);
     return;
   }
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
-    const int r = row_g0 + rb_row0 + (e & 3) + 8 * (e >> 2) + 4 * kh;
+    const int r = row_g0 + rb_row0 + d6_acc_row(e) + 4 * kh;
     const float v = acc[e];
     if (cok && r < rows) L.out[(size_t)r * L.ldo + L.ocol0 + col] = v;
   }
@@ -94,15 +88,15 @@ __global__ __launch_bounds__(256) void mlp_rows_kernel(const RowsArgs g) {
   constexpr int kPre = 8;
   const int nv = g.k0 / (4 * TPR);
   const bool pre = !CHUNKED && g.vec4 && nv * 4 * TPR == g.k0 && nv <= kPre;
-  f32x4r nxt[kPre];
+  f32x4 nxt[kPre];
   auto gfetch = [&](const int t) {
     const int r = t * TR + lrow;
     const float *src = g.x + (size_t)(r < g.rows ? r : 0) * g.ldx + g.xcol0 + 4 * lq;
 #pragma unroll
     for (int i = 0; i < kPre; ++i)
       if (i < nv) {
-        nxt[i] = *reinterpret_cast<const f32x4r *>(src + 4 * TPR * i);
-        if (r >= g.rows) nxt[i] = f32x4r{0.f, 0.f, 0.f, 0.f};
+        nxt[i] = *reinterpret_cast<const f32x4 *>(src + 4 * TPR * i);
+        if (r >= g.rows) nxt[i] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
   };
   if (pre && (int)blockIdx.x < ntiles_rows) gfetch(blockIdx.x);
@@ -116,7 +110,7 @@ __global__ __launch_bounds__(256) void mlp_rows_kernel(const RowsArgs g) {
       float *dst = XA + lrow * LDA;
       if (g.vec4) {
         for (int c = 4 * lq; c < kw; c += 4 * TPR) {
-          const f32x4r v = *reinterpret_cast<const f32x4r *>(src + c);
+          const f32x4 v = *reinterpret_cast<const f32x4 *>(src + c);
 #pragma unroll
           for (int e = 0; e < 4; ++e) dst[c + e] = r < g.rows ? v[e] : 0.f;
         }
@@ -144,8 +138,7 @@ __global__ __launch_bounds__(256) void mlp_rows_kernel(const RowsArgs g) {
       float *Y = (l & 1) ? XA : XB;
       const int LD = (l & 1) ? LDB : LDA, LDY = (l & 1) ? LDA : LDB;
       const bool last = l == nl - 1;
-      const __amdgpu_buffer_rsrc_t srd =
-          __builtin_amdgcn_make_buffer_rsrc((void *)(L.w + (size_t)L.wrow0 * L.ldw), 0, (unsigned)((size_t)L.k * L.ldw * 4), 0x00020000);
+      const __amdgpu_buffer_rsrc_t srd = d6_buffer(L.w + (size_t)L.wrow0 * L.ldw, (unsigned)((size_t)L.k * L.ldw * 4));
       const int ldw_bytes = L.ldw * 4;
       const int ncol_tiles = (L.n + 31) >> 5;
       const int nblk = L.k >> 5;                      // blocks of 16 k-steps (k is a multiple of 32)
@@ -153,6 +146,7 @@ __global__ __launch_bounds__(256) void mlp_rows_kernel(const RowsArgs g) {
       // unconditional (past the end it re-reads the last block): behind a conditional fetch the compiler's s_waitcnt
       // vmcnt accounting assumes the shorter queue and drains the ring.  The first two blocks of a wave's first column
       // tile are requested BEFORE the barrier that completes the layer's input in LDS (weights do not depend on it).
+      // (The ring is walked twice below, per K-chunk and per work item: as ONE local routine it changed all three instantiations.)
       float bs[3][16];
       auto fetch = [&](float (&b)[16], uint32_t voff, int blk) {
         const int bb = blk < nblk ? blk : nblk - 1;
@@ -170,7 +164,7 @@ __global__ __launch_bounds__(256) void mlp_rows_kernel(const RowsArgs g) {
         const uint32_t voff = (uint32_t)(kh * L.ldw + col) * 4u;
         f32x16 acc;
 #pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+        for (int e = 0; e < 16; ++e) acc[e] = 0.f;      // (local form: d6_acc_zero changes this kernel's code)
         for (int b0 = 0; b0 < nblk; b0 += cblk) {
           if (b0 > 0) {
             __syncthreads();                    // every wave is done with the previous chunk
@@ -188,7 +182,7 @@ __global__ __launch_bounds__(256) void mlp_rows_kernel(const RowsArgs g) {
 #pragma unroll
               for (int u = 0; u < 16; ++u) a[u] = xa[2 * u];
 #pragma unroll
-              for (int u = 0; u < 16; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u], acc, 0, 0, 0);
+              for (int u = 0; u < 16; ++u) d6_mfma(a[u], b[u], acc);
             };
             const int bend = b0 + cblk;
             int blk = b0;
@@ -224,15 +218,14 @@ __global__ __launch_bounds__(256) void mlp_rows_kernel(const RowsArgs g) {
         const int col = 32 * j + l31;
         const uint32_t voff = (uint32_t)(kh * L.ldw + col) * 4u;
         f32x16 acc;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+        d6_acc_zero(acc);
         auto compute = [&](const float (&b)[16], int blk) {
           const float *xa = X + (32 * rb + l31) * LD + 32 * blk + kh;
           float a[16];
 #pragma unroll
           for (int u = 0; u < 16; ++u) a[u] = xa[2 * u];
 #pragma unroll
-          for (int u = 0; u < 16; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u], acc, 0, 0, 0);
+          for (int u = 0; u < 16; ++u) d6_mfma(a[u], b[u], acc);
         };
         if (item != wave) {
           fetch(bs[0], voff, 0);
@@ -274,15 +267,14 @@ template <int NBLK, int NB>
 __device__ __forceinline__ f32x16 rows_item(const float *xa, const float (&b)[NB]) {
   static_assert(16 * NBLK <= NB, "the fragment array holds the layer");
   f32x16 acc;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+  d6_acc_zero(acc);
 #pragma unroll
   for (int blk = 0; blk < NBLK; ++blk) {
     float a[16];
 #pragma unroll
     for (int u = 0; u < 16; ++u) a[u] = xa[32 * blk + 2 * u];
 #pragma unroll
-    for (int u = 0; u < 16; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[16 * blk + u], acc, 0, 0, 0);
+    for (int u = 0; u < 16; ++u) d6_mfma(a[u], b[16 * blk + u], acc);
   }
   return acc;
 }
@@ -301,13 +293,11 @@ __global__ __launch_bounds__(256) void mlp_rows_resident_kernel(const RowsArgs g
   const det6d_rows_layer &LX = second ? L1 : L2;
   float b0[K0 / 2], bx[K1 / 2];
   {
-    const __amdgpu_buffer_rsrc_t srd0 =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(L0.w + (size_t)L0.wrow0 * L0.ldw), 0, (unsigned)((size_t)L0.k * L0.ldw * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t srd0 = d6_buffer(L0.w + (size_t)L0.wrow0 * L0.ldw, (unsigned)((size_t)L0.k * L0.ldw * 4));
     const uint32_t voff0 = (uint32_t)(kh * L0.ldw + 32 * j0 + l31) * 4u;
 #pragma unroll
     for (int u = 0; u < K0 / 2; ++u) b0[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srd0, voff0, 2 * u * L0.ldw * 4, 0));
-    const __amdgpu_buffer_rsrc_t srdx =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(LX.w + (size_t)LX.wrow0 * LX.ldw), 0, (unsigned)((size_t)LX.k * LX.ldw * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t srdx = d6_buffer(LX.w + (size_t)LX.wrow0 * LX.ldw, (unsigned)((size_t)LX.k * LX.ldw * 4));
     const uint32_t voffx = (uint32_t)(kh * LX.ldw + l31) * 4u;
     const int kx = second ? K1 / 2 : K2 / 2;
 #pragma unroll
@@ -320,14 +310,14 @@ __global__ __launch_bounds__(256) void mlp_rows_resident_kernel(const RowsArgs g
   const float shx = (cokx && LX.shift) ? LX.shift[l31] : 0.f;
   const int ntiles = (g.rows + TR - 1) / TR;
   const int lrow = tid >> 2, lq = tid & 3;
-  f32x4r nxt[NV];
+  f32x4 nxt[NV];
   auto gload = [&](const int tile) {
     const int r = tile * TR + lrow;
     const float *src = g.x + (size_t)(r < g.rows ? r : 0) * g.ldx + g.xcol0 + 4 * lq;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      nxt[i] = *reinterpret_cast<const f32x4r *>(src + 16 * i);
-      if (r >= g.rows) nxt[i] = f32x4r{0.f, 0.f, 0.f, 0.f};
+      nxt[i] = *reinterpret_cast<const f32x4 *>(src + 16 * i);
+      if (r >= g.rows) nxt[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
   };
   int tile = blockIdx.x;
@@ -347,7 +337,7 @@ __global__ __launch_bounds__(256) void mlp_rows_resident_kernel(const RowsArgs g
       const f32x16 acc = rows_item<K0 / 32>(XA + (32 * rb + l31) * LDA + kh, b0);
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int row = 32 * rb + (e & 3) + 8 * (e >> 2) + 4 * kh;
+        const int row = 32 * rb + d6_acc_row(e) + 4 * kh;
         float v = acc[e] + sh0;
         if (L0.act == 1) v = d6_relu(v);
         if (cok0) XB[row * LDB + col0] = v;
@@ -360,7 +350,7 @@ __global__ __launch_bounds__(256) void mlp_rows_resident_kernel(const RowsArgs g
       const f32x16 acc = rows_item<K1 / 32>(XB + (32 * rb + l31) * LDB + kh, bx);
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int row = 32 * rb + (e & 3) + 8 * (e >> 2) + 4 * kh;
+        const int row = 32 * rb + d6_acc_row(e) + 4 * kh;
         float v = acc[e] + shx;
         if (L1.act == 1) v = d6_relu(v);
         if (cokx) XA[row * LDA + l31] = v;
@@ -373,7 +363,7 @@ __global__ __launch_bounds__(256) void mlp_rows_resident_kernel(const RowsArgs g
       const f32x16 acc = rows_item<K2 / 32>(XA + (32 * rb + l31) * LDA + kh, bx);
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int row = 32 * rb + (e & 3) + 8 * (e >> 2) + 4 * kh;
+        const int row = 32 * rb + d6_acc_row(e) + 4 * kh;
         float v = acc[e] + shx;
         if (L2.act == 1) v = d6_relu(v);
         const int r = tile * TR + row;
@@ -424,8 +414,7 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_wave_kernel(const RowsArgs g)
   // layer 0's B fragments: k-step s, column tile j: W0[2 s + kh][32 j + l31]
   float b0[2][K0 / 2];
   {
-    const __amdgpu_buffer_rsrc_t srd0 =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(L0.w + (size_t)L0.wrow0 * L0.ldw), 0, (unsigned)((size_t)L0.k * L0.ldw * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t srd0 = d6_buffer(L0.w + (size_t)L0.wrow0 * L0.ldw, (unsigned)((size_t)L0.k * L0.ldw * 4));
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const uint32_t voff = (uint32_t)(kh * L0.ldw + 32 * j + l31) * 4u;
@@ -443,10 +432,10 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_wave_kernel(const RowsArgs g)
   __syncthreads();                                   // W1s / W2s staged: the only workgroup barrier
 
   // every tile is whole (the launcher asks for rows % 32 == 0) and every buffer is addressed with 32-bit byte offsets
-  const __amdgpu_buffer_rsrc_t srd_x = __builtin_amdgcn_make_buffer_rsrc((void *)(g.x + g.xcol0), 0, 0xffffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t srd_y0 = __builtin_amdgcn_make_buffer_rsrc((void *)(L0.out ? L0.out + L0.ocol0 : g.x), 0, 0xffffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t srd_y1 = __builtin_amdgcn_make_buffer_rsrc((void *)(L1.out ? L1.out + L1.ocol0 : g.x), 0, 0xffffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t srd_y2 = __builtin_amdgcn_make_buffer_rsrc((void *)(L2.out + L2.ocol0), 0, 0xffffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t srd_x = d6_buffer(g.x + g.xcol0);
+  const __amdgpu_buffer_rsrc_t srd_y0 = d6_buffer(L0.out ? L0.out + L0.ocol0 : g.x);
+  const __amdgpu_buffer_rsrc_t srd_y1 = d6_buffer(L1.out ? L1.out + L1.ocol0 : g.x);
+  const __amdgpu_buffer_rsrc_t srd_y2 = d6_buffer(L2.out + L2.ocol0);
   uint32_t xin[NJ], xls[NJ];                         // per lane: byte offset of its float4 in the rows / in the LDS image
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
@@ -460,14 +449,14 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_wave_kernel(const RowsArgs g)
 
   const int ntiles = g.rows / 32;
   const int stride = gridDim.x * 4;
-  f32x4r nxt[4][NJ];
+  f32x4 nxt[4][NJ];
   auto gload = [&](const int tile) {
     const int s0 = tile * 4 * ldx8;
 #pragma unroll
     for (int bq = 0; bq < 4; ++bq)
 #pragma unroll
       for (int j = 0; j < NJ; ++j)
-        nxt[bq][j] = __builtin_bit_cast(f32x4r, __builtin_amdgcn_raw_buffer_load_b128(srd_x, xin[j], s0 + bq * ldx8, 0));
+        nxt[bq][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_x, xin[j], s0 + bq * ldx8, 0));
   };
   int tile = blockIdx.x * 4 + wave;
   if (tile < ntiles) gload(tile);
@@ -482,14 +471,11 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_wave_kernel(const RowsArgs g)
         for (int e = 0; e < 4; ++e) dst[e] = nxt[bq][j][e];
       }
     if (tile + stride < ntiles) gload(tile + stride);            // in flight during this tile's three layers
-    __builtin_amdgcn_s_waitcnt(0xC07F);                          // lgkmcnt(0): the tile is in LDS (this wave wrote all of it)
-    __builtin_amdgcn_wave_barrier();
+    d6_lds_wave_sync();                          // lgkmcnt(0): the tile is in LDS (this wave wrote all of it)
     // ---- layer 0: two column tiles share every A fragment ----
     f32x16 a0[2];
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) a0[j][e] = 0.f;
+    for (int j = 0; j < 2; ++j) d6_acc_zero(a0[j]);
     {
       const float *xa = X + l31 * LD0 + kh;
 #pragma unroll
@@ -499,8 +485,8 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_wave_kernel(const RowsArgs g)
         for (int u = 0; u < 16; ++u) a[u] = xa[32 * blk + 2 * u];
 #pragma unroll
         for (int u = 0; u < 16; ++u) {
-          a0[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b0[0][16 * blk + u], a0[0], 0, 0, 0);
-          a0[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b0[1][16 * blk + u], a0[1], 0, 0, 0);
+          d6_mfma(a[u], b0[0][16 * blk + u], a0[0]);
+          d6_mfma(a[u], b0[1][16 * blk + u], a0[1]);
         }
       }
     }
@@ -519,29 +505,23 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_wave_kernel(const RowsArgs g)
         for (int e = 0; e < 16; ++e) a0[j][e] = a0[j][e] + sh0[j];
     }
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      float *xw = X + (4 * kh) * LD1 + 32 * j + l31;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) xw[((e & 3) + 8 * (e >> 2)) * LD1] = a0[j][e];
-    }
+    for (int j = 0; j < 2; ++j) d6_acc_to_lds(a0[j], X + (4 * kh) * LD1 + 32 * j + l31, LD1);
     if (out0) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const uint32_t voff = vrow * (uint32_t)ldo0 + (uint32_t)(32 * j + l31) * 4u;
+        // (local form, as in the two layers below: d6_acc_store_rows, or one epilogue routine used three times, changes this kernel)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          // (a local copy: __builtin_bit_cast straight on the vector ELEMENT stored element 0 sixteen times — seen in the ISA)
           const float v = a0[j][e];
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), srd_y0, voff, ((e & 3) + 8 * (e >> 2)) * ldo0, 0);
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), srd_y0, voff, d6_acc_row(e) * ldo0, 0);
         }
       }
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_wave_barrier();
+    d6_lds_wave_sync();
     // ---- layer 1 ----
     f32x16 a1;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) a1[e] = 0.f;
+    d6_acc_zero(a1);
     {
       const float *xa = X + l31 * LD1 + kh;
       const float *wb = W1s + kh * 32 + l31;
@@ -551,7 +531,7 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_wave_kernel(const RowsArgs g)
 #pragma unroll
         for (int u = 0; u < 16; ++u) { a[u] = xa[32 * blk + 2 * u]; b[u] = wb[(32 * blk + 2 * u) * 32]; }
 #pragma unroll
-        for (int u = 0; u < 16; ++u) a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u], a1, 0, 0, 0);
+        for (int u = 0; u < 16; ++u) d6_mfma(a[u], b[u], a1);
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -562,25 +542,19 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_wave_kernel(const RowsArgs g)
 #pragma unroll
       for (int e = 0; e < 16; ++e) a1[e] = a1[e] + sh1;
     }
-    {
-      float *xw = X + (4 * kh) * LD2 + l31;          // (L1.n == K2 == 32: every column is a real one)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) xw[((e & 3) + 8 * (e >> 2)) * LD2] = a1[e];
-    }
+    d6_acc_to_lds(a1, X + (4 * kh) * LD2 + l31, LD2);          // (L1.n == K2 == 32: every column is a real one)
     if (out1 && cok1) {
       const uint32_t voff = vrow * (uint32_t)ldo1 + (uint32_t)l31 * 4u;
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const float v = a1[e];
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), srd_y1, voff, ((e & 3) + 8 * (e >> 2)) * ldo1, 0);
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), srd_y1, voff, d6_acc_row(e) * ldo1, 0);
       }
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_wave_barrier();
+    d6_lds_wave_sync();
     // ---- layer 2 ----
     f32x16 a2;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) a2[e] = 0.f;
+    d6_acc_zero(a2);
     {
       const float *xa = X + l31 * LD2 + kh;
       const float *wb = W2s + kh * 32 + l31;
@@ -588,7 +562,7 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_wave_kernel(const RowsArgs g)
 #pragma unroll
       for (int u = 0; u < 16; ++u) { a[u] = xa[2 * u]; b[u] = wb[(2 * u) * 32]; }
 #pragma unroll
-      for (int u = 0; u < 16; ++u) a2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u], a2, 0, 0, 0);
+      for (int u = 0; u < 16; ++u) d6_mfma(a[u], b[u], a2);
     }
     __builtin_amdgcn_wave_barrier();
     if (relu2) {
@@ -603,7 +577,7 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_wave_kernel(const RowsArgs g)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const float v = a2[e];
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), srd_y2, voff, ((e & 3) + 8 * (e >> 2)) * ldo2, 0);
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), srd_y2, voff, d6_acc_row(e) * ldo2, 0);
       }
     }
   }
@@ -690,8 +664,10 @@ DET6D_API int det6d_mlp_rows(int rows, const float *x, int ldx, int xcol0, int n
   g.fits32 = fits32 ? 1 : 0;
   // (the wave-private kernel forms its scalar byte offsets in signed 32-bit arithmetic: half the range)
   const bool fits31 = fits32 && (size_t)rows * ldx * 4 < 0x7ff00000ull;
-  if (resident_env == 2 && nchains == 1 && nlayers[0] == 3 && g.kchunk == g.k0 && g.vec4 && rows >= 16384 && (rows & 31) == 0 && fits31 &&
-      layers[0].k == 96 && layers[0].n == 64 && layers[1].n == 32 && layers[2].n <= 32 && layers[0].ldw >= 64 && layers[1].ldw >= 32) {
+  // the SA1 shape [96 -> 64 -> 32 -> n <= 32] over many rows, whole input in LDS
+  const bool sa1 = nchains == 1 && nlayers[0] == 3 && g.kchunk == g.k0 && g.vec4 && rows >= 16384 && layers[0].k == 96 &&
+                   layers[0].n == 64 && layers[1].n == 32 && layers[2].n <= 32 && layers[0].ldw >= 64 && layers[1].ldw >= 32;
+  if (sa1 && resident_env == 2 && (rows & 31) == 0 && fits31) {
     constexpr size_t lds_wave = sizeof(float) * ((64 + 32) * 32 + 4 * 32 * 97);
     DET6D_MAX_DYNAMIC_LDS((mlp_rows_wave_kernel<96, 64, 32>), lds_wave);
     int blocks = ((rows + 31) / 32 + 3) / 4;
@@ -699,8 +675,7 @@ DET6D_API int det6d_mlp_rows(int rows, const float *x, int ldx, int xcol0, int n
     hipLaunchKernelGGL((mlp_rows_wave_kernel<96, 64, 32>), dim3(blocks), dim3(256), lds_wave, (hipStream_t)stream, g);
     return det6d_check_launch("det6d_mlp_rows");
   }
-  if (resident_env && nchains == 1 && nlayers[0] == 3 && g.kchunk == g.k0 && g.vec4 && rows >= 16384 && layers[0].k == 96 &&
-      layers[0].n == 64 && layers[1].n == 32 && layers[2].n <= 32 && layers[0].ldw >= 64 && layers[1].ldw >= 32) {
+  if (sa1 && resident_env) {
     constexpr size_t lds_resident = sizeof(float) * (2 * 64 * 97 + 64 * 65);
     DET6D_MAX_DYNAMIC_LDS((mlp_rows_resident_kernel<96, 64, 32>), lds_resident);
     int blocks = (rows + 63) / 64;
@@ -717,13 +692,10 @@ DET6D_API int det6d_mlp_rows(int rows, const float *x, int ldx, int xcol0, int n
   const int rb = (rb_env >= 2 && g.kchunk == g.k0 && max_tiles <= 2 && (rows >= 16384 || rb_env == 3)) ? 2 : 1;
   const size_t lds_bytes = sizeof(float) * 32 * rb * ((size_t)(g.wa + 1) + (size_t)(g.wb + 1));
   if (lds_bytes > 160 * 1024) return DET6D_EINVAL;
-  static size_t attr_bytes = 0;
-  if (lds_bytes > attr_bytes) {
-    hipFuncSetAttribute((const void *)mlp_rows_kernel<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    hipFuncSetAttribute((const void *)mlp_rows_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    hipFuncSetAttribute((const void *)mlp_rows_kernel<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    attr_bytes = lds_bytes;
-  }
+  // (the need varies per call: the limit is set once per device, to the CU's 160 KB)
+  DET6D_MAX_DYNAMIC_LDS((mlp_rows_kernel<false, 1>), 160 * 1024);
+  DET6D_MAX_DYNAMIC_LDS((mlp_rows_kernel<true, 1>), 160 * 1024);
+  DET6D_MAX_DYNAMIC_LDS((mlp_rows_kernel<false, 2>), 160 * 1024);
   int blocks = (rows + 32 * rb - 1) / (32 * rb);
   // persistent walk over the tiles by as many workgroups as the chip HOLDS at a time (LDS: 3 per CU for the SA stacks; 128
   // registers: at most 4): a grid of 1024 on 768 slots ran its last 256 workgroups on a third of the chip (80-scene passes,

@@ -430,3 +430,25 @@ def test_plain_layer_stacks_equal_the_layer_by_layer_oracle(oracle_ops, rows_n):
     r2 = oracle_ops.linear(oracle_ops.linear(x2, t2a[0][:, :128], t2a[1], 1), t2b[0][:, :32], t2b[1], 0)
     np.testing.assert_array_equal(o1.cpu().numpy(), r1)
     np.testing.assert_array_equal(o2.cpu().numpy(), r2)
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two devices")
+def test_rows_lds_limit_is_set_on_every_device(oracle_ops):
+    """csrc/mlp_rows.hip: the dynamic-LDS limit of a kernel is a per-DEVICE property.  One chain [480 -> 256 -> 32] over 64 rows
+    (15 blocks of 16 k-steps, eight column tiles) takes 32 x (481 + 257) x 4 = 94 464 bytes of LDS: above the 64 KB default,
+    not K-chunked (k0 < 512).  First on device 0, then on device 1 — which a process-wide "limit is set" flag left at the
+    default, so that the second launch failed; == oracle linear, layer by layer, on both"""
+    from de6d_amd.ops import fused
+    rng = np.random.default_rng(480)
+    x = rng.normal(size=(64, 480)).astype(np.float32)
+    w1 = (rng.normal(size=(480, 256)) / np.sqrt(480)).astype(np.float32)
+    w2 = (rng.normal(size=(256, 32)) / np.sqrt(256)).astype(np.float32)
+    s1, s2 = rng.normal(size=(256,)).astype(np.float32), rng.normal(size=(32,)).astype(np.float32)
+    ref = oracle_ops.linear(oracle_ops.linear(x, w1, s1, 1), w2, s2, 1)
+    for d in (0, 1):
+        with torch.cuda.device(d):
+            out = torch.empty((64, 32), device="cuda")
+            spec = [(dev(w1), 0, dev(s1), 480, 256, 1, None, 0), (dev(w2), 0, dev(s2), 256, 32, 1, out, 0)]
+            assert fused.mlp_rows_eligible(480, [spec])
+            fused.mlp_rows(dev(x), 0, [spec])
+            np.testing.assert_array_equal(out.cpu().numpy(), ref)

@@ -16,7 +16,20 @@
 //    (2 x 2048 matrix cycles) ahead of their use, per-lane offset computed once and
 //    the k / column offsets as scalars: the K loops contain no barrier, no LDS store and no vector-ALU instruction
 //    (on gfx950 the fp32 MFMA shares the vector ALU: DESIGN.md §8);
-//  * two workgroup barriers per tile (after the first layer is in LDS, after the second), none inside a layer.
+//  * two workgroup barriers per tile (after the first layer is in LDS, after the second), none inside a layer;
+//  * a tile starts with ONE memory round trip: its rows' list entries were requested during the tile before, and the first
+//    layer requests everything else it reads — the rows' chunks of P, their points and centres, W1's coordinate rows and the
+//    shift — in one batch of a compile-time number of loads before its first use (group_layer1); the ticket of the next
+//    tile is drawn behind that batch, so its answer is waited for together with the gather's.  Per instantiation:
+//      streaming [256 -> 512 -> 1024], [256 -> 256 -> 512] (head, default route): W1's rows and the shift are staged in LDS
+//        once per workgroup (4 KB on top of 66 KB: two workgroups per CU as before); the batch is 8 chunks of P + point +
+//        centre, with 16 LDS reads beside it; 243 / 156 registers (244 / 155 before), 2 / 3 waves per SIMD;
+//      one-pass [128 -> 128 -> 256], [128 -> 256 -> 256] with four waves (SA3, default route): 3 x 51.7 KB of the CU's 160 KB
+//        and 168 registers at three workgroups per CU leave room for neither an LDS copy nor 64 registers of W1, so W1 and
+//        the shift come from the cache: the batch holds the 4 chunks of P, point, centre and the first two of the four
+//        chunks of W1 / shift (8 loads), the other two are requested before the first chunk is consumed; 156 / 159
+//        registers (136 / 148 before), 3 waves per SIMD;
+//      streaming [128 -> 256 -> 256] and the other one-pass forms (off the default route): from the cache in the same way.
 // Arithmetic: every output is the oracle's chain (features ascending, then dx, dy, dz for layer 1; k ascending for
 // layers 2, 3; + shift; ReLU; max over the rows of a centre) — bit-identical to the three-launch path.
 #include "common.h"
@@ -39,7 +52,7 @@ struct GroupArgs {
   const int *idx; int n, m, ns; const int *cnt;   // dense rows
   const int *hdr; const int *crow_p; const int *crow_c;   // compact rows
   float *y; int ldy; int col0;
-  int pre;                                        // A/B switch: list entries of the next tile requested a K loop ahead
+  int pre;                                        // A/B switch: list entries of the next tile requested ahead (0: inside the first layer)
   int yvec;                                       // y rows are 16-byte aligned (ldy, col0 multiples of 4): vector stores allowed
   int *ticket;                                    // compact rows: tile ticket + exit counter (hdr + kCompactHdrTicket); nullptr: static tiles
 };
@@ -50,8 +63,8 @@ struct GroupArgs {
 // host a sampler workgroup (16 waves at raised priority for 2 ms), others a ball-query or list-builder wave — the wide head
 // group ran 1.5-1.6 ms per launch under load against 0.98 ms alone.  Now a workgroup takes its FIRST tile by its block index
 // and every further one from a ticket counter in the list header: fast CUs take more tiles.  The ticket of the next tile is
-// drawn at the top of the current one (its latency hides behind the gather), published through LDS by tile parity, so the
-// next tile's list entries can still be requested a K loop ahead.  The counter pair cleans itself: the last workgroup to leave
+// drawn inside the current one's first layer, behind the gather's requests (group_layer1), published through LDS by tile parity, so the
+// next tile's list entries can still be requested ahead.  The counter pair cleans itself: the last workgroup to leave
 // (exit counter == workgroups that had a tile) zeroes both, so a launch may be replayed without rebuilding the list
 // (bench: family_saturated); compact_place_kernel zeroes them too when it builds the list.  Results do not depend on which
 // workgroup computes a tile (a tile's outputs are a function of its rows; multi-part centres combine by an order-independent
@@ -229,7 +242,9 @@ struct GroupLayer {
 // produces columns 4q + 4 EPR i of its row:
 // X1[row][c] = relu(fma(dz, W1[2][c], fma(dy, W1[1][c], fma(dx, W1[0][c], P[p][c]))) + s1[c]) ----
 // The row's list entry (compact: tag + point row; dense: neighbour index) is the first of two dependent global loads of the
-// gather; group_row_entry() requests it for the NEXT tile before the current tile's third layer (ahead by a whole K loop).
+// gather; group_row_entry() requests it for the NEXT tile during the current one: before its third layer in the one-pass
+// kernel (ahead by a whole K loop), right after its first barrier — where the next tile's number is known — in the streaming
+// kernel (ahead by a whole tile).  A tile past the end re-reads its own entries.
 template <bool COMPACT, int EPR>
 __device__ __forceinline__ void group_row_entry(const GroupArgs &g, const int tile, const int tid, int &e0, int &e1) {
   const int r = tile * 32 + tid / EPR;
@@ -237,48 +252,90 @@ __device__ __forceinline__ void group_row_entry(const GroupArgs &g, const int ti
   else { e0 = g.idx[r]; e1 = 0; }
 }
 
-template <int C1, bool COMPACT, int EPR>
+//
+// One round trip per tile: a thread's trip count is a compile-time constant (NI = C1 / (4 EPR) chunks of four columns), and
+// everything the tile needs from memory is requested in ONE batch before the first use — the NI chunks of P, the point and
+// the centre (three dwords each; their addresses hang on the list entry alone, like P's) and the tile-invariant operands
+// (W1's three coordinate rows and the shift).  Alignment rows (tag < 0) gather row 0 / centre 0 — in bounds, the values are
+// dropped — and write zeros.  (A loop that starts at the lane's own column, `for (c = 4 * eq; c < C1; c += 4 * EPR)`, is
+// compiled rolled, "loop not unrolled": a wait for its five loads in every iteration, behind a wait for the point and the
+// centre — NI + 1 dependent round trips per tile.)
+// W1S: the tile-invariant operands come from LDS (rows wx, wy, wz, shift of C1 floats each, staged once per workgroup by
+// group_stage_w1) instead of from the cache in the same batch.
+template <int C1>
+__device__ __forceinline__ void group_stage_w1(const GroupArgs &g, const int tid, const int nthreads, float *__restrict__ W1s) {
+  for (int c = 4 * tid; c < 4 * C1; c += 4 * nthreads) {
+    const int row = c / C1, col = c % C1;
+    const float *src = row < 3 ? g.w1 + row * g.ldw1 + col : g.s1 + col;
+    *reinterpret_cast<f32x4 *>(W1s + c) = *reinterpret_cast<const f32x4 *>(src);
+  }
+}
+
+template <int C1, bool COMPACT, int EPR, bool W1S, int WB>
 __device__ __forceinline__ void group_layer1(const GroupArgs &g, const int tile, const int tid, float *__restrict__ X1,
-                                             int *__restrict__ tagbuf, const int e0, const int e1) {
+                                             int *__restrict__ tagbuf, const int e0, const int e1, const float *__restrict__ W1s,
+                                             int *const ticket, int &drawn) {
   constexpr int LD1 = C1 + 1;
+  constexpr int NI = C1 / (4 * EPR);          // chunks of four columns per thread
+  static_assert(C1 % (4 * EPR) == 0 && NI >= 1, "a row's columns divide evenly among its EPR threads");
   const int erow = tid / EPR, eq = tid % EPR;
-    {
-      const int r = tile * 32 + erow;
-      long long prow;
-      int cj;
-      bool real = true;
-      if (COMPACT) {
-        const int tag = e0;
-        if (eq == 0) tagbuf[erow] = tag;     // the pooling epilogue takes the rows' tags from LDS (visible after the barrier)
-        real = tag >= 0;
-        cj = d6_compact_centre(tag);
-        prow = e1;
-      } else {
-        cj = r / g.ns;
-        prow = (long long)(cj / g.m) * g.n + e0;
-      }
-      float dx = 0.f, dy = 0.f, dz = 0.f;
-      if (real) {
-        const float *pt = g.pts + prow * g.ldpts;
-        const float *ce = g.ctr + (long long)cj * g.ldctr;
-        dx = pt[0] - ce[0]; dy = pt[1] - ce[1]; dz = pt[2] - ce[2];
-      }
-      const float *prow_p = g.p + (real ? prow : 0) * g.ldp + g.pcol0;
-      float *xr = X1 + erow * LD1;
-#pragma unroll 4
-      for (int c = 4 * eq; c < C1; c += 4 * EPR) {
-        const f32x4 pv = *reinterpret_cast<const f32x4 *>(prow_p + c);
-        const f32x4 wx = *reinterpret_cast<const f32x4 *>(g.w1 + c);
-        const f32x4 wy = *reinterpret_cast<const f32x4 *>(g.w1 + g.ldw1 + c);
-        const f32x4 wz = *reinterpret_cast<const f32x4 *>(g.w1 + 2 * g.ldw1 + c);
-        const f32x4 sh = *reinterpret_cast<const f32x4 *>(g.s1 + c);
+  const int r = tile * 32 + erow;
+  long long prow;
+  int cj;
+  bool real = true;
+  if (COMPACT) {
+    const int tag = e0;
+    if (eq == 0) tagbuf[erow] = tag;     // the pooling epilogue takes the rows' tags from LDS (visible after the barrier)
+    real = tag >= 0;
+    cj = real ? d6_compact_centre(tag) : 0;
+    prow = real ? e1 : 0;
+  } else {
+    cj = r / g.ns;
+    prow = (long long)(cj / g.m) * g.n + e0;
+  }
+  const float *prow_p = g.p + prow * g.ldp + g.pcol0 + 4 * eq;
+  const float *pt = g.pts + prow * g.ldpts;
+  const float *ce = g.ctr + (long long)cj * g.ldctr;
+  // the batch: the tile's own operands and the first WB chunks of the tile-invariant ones; chunk i + WB of those is requested
+  // before chunk i is consumed (WB = NI where the registers hold all of them)
+  f32x4 pv[NI], wx[NI], wy[NI], wz[NI], sh[NI];
+  const float *wrow = (W1S ? W1s : g.w1) + 4 * eq, *srow = (W1S ? W1s + 3 * C1 : g.s1) + 4 * eq;
+  const int ldw = W1S ? C1 : g.ldw1;
+  auto fetch_w = [&](const int i) {
+    wx[i] = *reinterpret_cast<const f32x4 *>(wrow + 4 * EPR * i);
+    wy[i] = *reinterpret_cast<const f32x4 *>(wrow + ldw + 4 * EPR * i);
+    wz[i] = *reinterpret_cast<const f32x4 *>(wrow + 2 * ldw + 4 * EPR * i);
+    sh[i] = *reinterpret_cast<const f32x4 *>(srow + 4 * EPR * i);
+  };
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float v = d6_relu(D6_FMA(dz, wz[e], D6_FMA(dy, wy[e], D6_FMA(dx, wx[e], pv[e]))) + sh[e]);
-          xr[c + e] = real ? v : 0.f;
-        }
-      }
+  for (int i = 0; i < NI; ++i) pv[i] = *reinterpret_cast<const f32x4 *>(prow_p + 4 * EPR * i);
+  float px = pt[0], py = pt[1], pz = pt[2];
+  const float cx = ce[0], cy = ce[1], cz = ce[2];
+#pragma unroll
+  for (int i = 0; i < (WB < NI ? WB : NI); ++i) fetch_w(i);
+  __builtin_amdgcn_sched_barrier(0);     // all of them requested before the first wait (left alone, the scheduler holds requests back)
+  // The next tile's ticket is drawn HERE, behind the batch: the compiler folds a wave's draw into one atomic and reads its
+  // result back at once (s_waitcnt vmcnt(0), v_readfirstlane), so drawn at the tile's top it was a round trip of its own in
+  // front of the gather for wave 0, on which the tile's first barrier then waited; here its wait is the gather's.
+  if (ticket && tid == 0) drawn = g_draw_ticket(ticket, (int)gridDim.x);
+  float *xr = X1 + erow * LD1 + 4 * eq;
+  float dx = 0.f, dy = 0.f, dz = 0.f;
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    if (i + WB < NI) {
+      fetch_w(i + WB);
+      __builtin_amdgcn_sched_barrier(0);
     }
+    if (i == 0) {                          // the first wait
+      asm volatile("" : "+v"(px), "+v"(py), "+v"(pz));     // (the subtractions do not move up past the requests above)
+      dx = px - cx; dy = py - cy; dz = pz - cz;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float v = d6_relu(D6_FMA(dz, wz[i][e], D6_FMA(dy, wy[i][e], D6_FMA(dx, wx[i][e], pv[i][e]))) + sh[i][e]);
+      xr[4 * EPR * i + e] = real ? v : 0.f;
+    }
+  }
 }
 
 // ---- max-pool of the third layer's accumulators over the rows of a centre + shift + ReLU + store (compact rows: class
@@ -373,6 +430,7 @@ template <int C1, int C2, int C3, bool COMPACT, int NW>
 __global__ __launch_bounds__(64 * NW, (NW == 4 && C3 <= 256) ? 3 : 1) void mlp_group_kernel(const GroupArgs g) {
   D6_GEMM_PRIO_APPLY();
   constexpr int LD1 = C1 + 1, LD2 = C2 + 1;
+  constexpr int WB1 = NW == 4 ? (C3 <= 256 ? 1 : 2) : 4;
   constexpr int TN2 = C2 / (32 * NW), TN3 = C3 / (32 * NW);     // accumulator tiles per wave: a wave owns 1 / NW of every layer's columns
   static_assert(TN2 >= 1 && TN3 >= 1, "every wave needs at least one 32-column tile per layer");
   extern __shared__ float lds[];
@@ -382,6 +440,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && C3 <= 256) ? 3 : 1) void mlp_g
   int it = 0;                                                     // epilogue and the next tile's first layer)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, kh = lane >> 5;
   float *scr = reinterpret_cast<float *>(tags + 64) + wave * (64 * kGroupVW<TN3>);   // wave-private: g_store_group
+  // the drawn tile by tile parity; in the dynamic region (a static array ahead of it would move its base off 16 bytes)
+  int *next_tile_s = reinterpret_cast<int *>(reinterpret_cast<float *>(tags + 64) + NW * (64 * kGroupVW<TN3>));
   const int live_tiles = (COMPACT ? g.hdr[kCompactHdrLive] : g.rows) / 32;
   if ((int)blockIdx.x >= live_tiles) return;
   int h1 = 0, h2 = 0, h3 = 0, h4 = 0, h5 = 0;
@@ -400,21 +460,19 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && C3 <= 256) ? 3 : 1) void mlp_g
   D6_PHASE_DECL
   int e0, e1;
   group_row_entry<COMPACT, 2 * NW>(g, blockIdx.x, tid, e0, e1);
-  __shared__ int next_tile_s[2];
   int *const ticket = COMPACT ? g.ticket : nullptr;
   for (int tile = blockIdx.x; tile < live_tiles;) {
 #ifdef DET6D_EXPERIMENTS
     ++ph_tiles;
 #endif
-    int drawn = 0;
-    if (ticket && tid == 0) drawn = g_draw_ticket(ticket, (int)gridDim.x);
+    int drawn = 0;                         // tiles by ticket: see g_draw_ticket; drawn inside the first layer
     GroupLayer<C1, TN2, LD1> second;
     GroupLayer<C2, TN3, LD2> third;
     second.start(srd2, voff2, g.ldw2 * 4);
     const int par = it & 1;
     int *tagbuf = tags + 32 * (it++ & 1);
     if (!g.pre) group_row_entry<COMPACT, 2 * NW>(g, tile, tid, e0, e1);
-    group_layer1<C1, COMPACT, 2 * NW>(g, tile, tid, X1, tagbuf, e0, e1);
+    group_layer1<C1, COMPACT, 2 * NW, false, WB1>(g, tile, tid, X1, tagbuf, e0, e1, nullptr, ticket, drawn);
     if (ticket && tid == 0) next_tile_s[par] = drawn;
     __syncthreads();
     const int next_tile = ticket ? next_tile_s[par] : tile + (int)gridDim.x;
@@ -517,6 +575,12 @@ __device__ __forceinline__ void stream_layer(const float *__restrict__ X, const 
   }
 }
 
+// The tile-invariant first-layer operands (W1's coordinate rows, the shift) are staged in LDS once per workgroup where that
+// costs no residency: the head's groups (C1 = 256) hold 66 KB, two workgroups per CU with or without the 4 KB.  SA3's wide
+// group in this form (C1 = 128, DET6D_GROUP_STREAM bit 4) fits three workgroups in the CU's 160 KB with 2 KB to spare and keeps
+// reading them from the cache, in the gather's batch.
+template <int C1> constexpr bool kStreamStagesW1 = C1 >= 256;
+
 template <int C1, int C2, int C3, bool COMPACT>
 __global__ __launch_bounds__(256, 2) void mlp_group_stream_kernel(const GroupArgs g) {
   D6_GEMM_PRIO_APPLY();
@@ -525,6 +589,7 @@ __global__ __launch_bounds__(256, 2) void mlp_group_stream_kernel(const GroupArg
   constexpr int LD1 = C1 + 1, LDY = CH + 1;
   constexpr int TN3 = C3 / 128;                    // accumulator tiles per wave in the third layer
   static_assert(C2 % CH == 0 && NCH >= 2 && TN3 >= 2, "chunk structure");
+  constexpr bool W1S = kStreamStagesW1<C1>;
   extern __shared__ float lds[];
   float *X1 = lds;
   float *Y0 = lds + 32 * LD1;
@@ -533,6 +598,8 @@ __global__ __launch_bounds__(256, 2) void mlp_group_stream_kernel(const GroupArg
   int it = 0;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, kh = lane >> 5;
   float *scr = reinterpret_cast<float *>(tags + 64) + wave * (64 * kGroupVW<TN3>);   // wave-private: g_store_group
+  float *W1s = reinterpret_cast<float *>(tags + 64) + 4 * (64 * kGroupVW<TN3>);       // W1S: 4 x C1 floats, 16-byte aligned
+  int *next_tile_s = reinterpret_cast<int *>(W1s + (W1S ? 4 * C1 : 0));              // the drawn tile by tile parity
   const int live_tiles = (COMPACT ? g.hdr[kCompactHdrLive] : g.rows) / 32;
   if ((int)blockIdx.x >= live_tiles) return;
   int h1 = 0, h2 = 0, h3 = 0, h4 = 0, h5 = 0;
@@ -557,19 +624,26 @@ __global__ __launch_bounds__(256, 2) void mlp_group_stream_kernel(const GroupArg
     for (int e = 0; e < 16; ++e) yc[(d6_acc_row(e) + 4 * kh) * LDY] = d6_relu(acc2[0][e] + sh2);
   };
 
-  __shared__ int next_tile_s[2];
+  int e0, e1;
+  group_row_entry<COMPACT, 8>(g, blockIdx.x, tid, e0, e1);
+  if (W1S) {
+    group_stage_w1<C1>(g, tid, 256, W1s);
+    __syncthreads();
+  }
   int *const ticket = COMPACT ? g.ticket : nullptr;
   for (int tile = blockIdx.x; tile < live_tiles;) {
-    int drawn = 0;
-    if (ticket && tid == 0) drawn = g_draw_ticket(ticket, (int)gridDim.x);     // tiles by ticket: see g_draw_ticket
+    int drawn = 0;                         // tiles by ticket: see g_draw_ticket; drawn inside the first layer
     const int par = it & 1;
     int *tagbuf = tags + 32 * (it++ & 1);
-    int e0, e1;
-    group_row_entry<COMPACT, 8>(g, tile, tid, e0, e1);
-    group_layer1<C1, COMPACT, 8>(g, tile, tid, X1, tagbuf, e0, e1);
+    if (!g.pre) group_row_entry<COMPACT, 8>(g, tile, tid, e0, e1);
+    group_layer1<C1, COMPACT, 8, W1S, 4>(g, tile, tid, X1, tagbuf, e0, e1, W1s, ticket, drawn);
     if (ticket && tid == 0) next_tile_s[par] = drawn;
     __syncthreads();
     const int next_tile = ticket ? next_tile_s[par] : tile + (int)gridDim.x;
+    if (g.pre) {          // the next tile's list entries, a whole tile ahead of its first layer (the last tile re-reads its own)
+      const int nt = next_tile;
+      group_row_entry<COMPACT, 8>(g, nt < live_tiles ? nt : tile, tid, e0, e1);
+    }
     f32x16 acc[TN3];
 #pragma unroll
     for (int j = 0; j < TN3; ++j) d6_acc_zero(acc[j]);
@@ -605,7 +679,8 @@ static int group_grid(int rows, size_t lds_bytes, int max_per_cu) {
 
 template <int C1, int C2, int C3, bool COMPACT>
 int launch_group_stream(const GroupArgs &g, hipStream_t stream) {
-  const size_t lds_bytes = sizeof(float) * (32 * (size_t)(C1 + 1 + 2 * 129) + 64 + 4 * 64 * kGroupVW<C3 / 128>);   // + tags + store scratch
+  const size_t lds_bytes = sizeof(float) * (32 * (size_t)(C1 + 1 + 2 * 129) + 64 + 4 * 64 * kGroupVW<C3 / 128> +   // + tags + store scratch
+                                            (kStreamStagesW1<C1> ? 4 * C1 : 0) + 4);                                // + W1 rows and shift + drawn tiles
   DET6D_MAX_DYNAMIC_LDS((mlp_group_stream_kernel<C1, C2, C3, COMPACT>), lds_bytes);
   const int blocks = group_grid(g.rows, lds_bytes, 3);      // 2 per CU for the head's groups (66 KB), 3 for SA3's (52 KB)
   hipLaunchKernelGGL((mlp_group_stream_kernel<C1, C2, C3, COMPACT>), dim3(blocks), dim3(256), lds_bytes, stream, g);
@@ -614,7 +689,7 @@ int launch_group_stream(const GroupArgs &g, hipStream_t stream) {
 
 template <int C1, int C2, int C3, bool COMPACT, int NW>
 int launch_group(const GroupArgs &g, hipStream_t stream) {
-  const size_t lds_bytes = sizeof(float) * (32 * (size_t)(C1 + 1 + C2 + 1) + 64 + NW * 64 * kGroupVW<C3 / (32 * NW)>);   // + tags + store scratch
+  const size_t lds_bytes = sizeof(float) * (32 * (size_t)(C1 + 1 + C2 + 1) + 64 + NW * 64 * kGroupVW<C3 / (32 * NW)> + 4);   // + tags + store scratch + drawn tiles
   DET6D_MAX_DYNAMIC_LDS((mlp_group_kernel<C1, C2, C3, COMPACT, NW>), lds_bytes);
   const int blocks = group_grid(g.rows, lds_bytes, 4);
 #ifdef DET6D_EXPERIMENTS

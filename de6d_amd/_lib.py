@@ -193,11 +193,14 @@ _EXT_SIGNATURES = {
     "det6d_ext_head_loss_backward": [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P],
     "det6d_ext_centerness_labels": [c_int, _P, _P, c_int, _P, _P, _P],
     "det6d_ext_corner_loss": [c_int, _P, c_int, _P, c_int, _P, _P],
+    "det6d_ext_linear_backward": [c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int,
+                                  _P, c_int, _P, _P, c_int64, _P],
 }
 #: every symbol include/det6d_ext.h declares (tests/test_ext_boundary.py checks the export table)
 EXT_EXPORTED_SYMBOLS = sorted(list(_EXT_SIGNATURES) + ["det6d_ext_version", "det6d_ext_last_error",
                                                           "det6d_ext_fps_features_workspace_bytes",
-                                                          "det6d_ext_head_loss_workspace_bytes"])
+                                                          "det6d_ext_head_loss_workspace_bytes",
+                                                          "det6d_ext_linear_backward_workspace_bytes"])
 _ext_lib = None
 
 
@@ -220,6 +223,8 @@ def ext_lib():
         handle.det6d_ext_fps_features_workspace_bytes.restype = c_int64
         handle.det6d_ext_head_loss_workspace_bytes.argtypes = [c_int]
         handle.det6d_ext_head_loss_workspace_bytes.restype = c_int64
+        handle.det6d_ext_linear_backward_workspace_bytes.argtypes = [c_int, c_int, c_int]
+        handle.det6d_ext_linear_backward_workspace_bytes.restype = c_int64
         _ext_lib = handle
     return _ext_lib
 

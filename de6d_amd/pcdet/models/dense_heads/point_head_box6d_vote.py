@@ -17,8 +17,16 @@ its gradient: build_losses, get_vote_layer_loss, generate_centerness_label, get_
 get_corner_loss_lidar and get_loss(tb_dict=None) under the reference's names, all reading self.forward_ret_dict, which
 prepare_loss(batch_dict) fills from an eval forward plus gt_boxes the way the reference's training forward would (:823-876).
 get_loss returns a 0-d tensor with a graph: loss.backward() reaches point_vote_coords, point_cls_preds and point_reg_preds of
-forward_ret_dict (prepare_loss(batch_dict, requires_grad=True) makes them leaves).  Differences from the reference, all of them
-kept on purpose:
+forward_ret_dict (prepare_loss(batch_dict, requires_grad=True) makes them leaves).
+Fine-tuning the towers: prepare_loss(batch_dict, requires_grad=True, towers=True) re-evaluates shared_fc_layer, cls_layers and
+reg_layers from the pooled vote features through ops.mlp_backward.FoldedChain (the forward kernels and the cached folded
+tensors of the eval forward: the same bits), so that loss.backward() leaves .grad on every parameter of the three stacks
+(conv.weight, bn.weight, bn.bias, the last conv.bias) and dL/d(pooled features) on forward_ret_dict['point_pooled_features'].
+BatchNorm stays frozen (eval mode: the reference's model.eval() plus grad).  vote_layers and everything before the pooled
+features get NO gradient: the true gradient of the vote coordinates also flows through the SA layer around the votes (grouped
+xyz - new_xyz), a path that does not exist here, and a vote-FC gradient from d_vote alone would silently differ from the
+reference's.  BatchNorm with batch statistics and a training-mode forward() stay out of scope.
+Differences from the reference, all of them kept on purpose:
   * tb_dict values are 0-d device tensors, not Python floats: nothing is read on the host, the call can be captured;
   * labels are constants.  The reference has no detach at :310, so a gradient leaks from the encoded offset labels back into
     the vote coordinates; here the labels come out of assign_training_targets without a graph;
@@ -42,7 +50,7 @@ import torch.nn as nn
 from ...ops.pointnet2.pointnet2_batch import pointnet2_modules
 from ...ops.pointnet2.pointnet2_batch.pointnet2_modules import fold_sequential, rows_ld, round4, run_chain, to_device
 from ...ops_backend import fused
-from ....ops import box_targets, head_loss
+from ....ops import box_targets, head_loss, mlp_backward
 from ...utils import box_coder_utils
 
 
@@ -191,7 +199,8 @@ class PointHeadBox6DVote(nn.Module):
         batch_dict['cls_preds_normalized'] = False
         batch_dict['point_reg_preds'] = point_reg_preds
         self.forward_ret_dict = {'batch_size': batch_size, 'point_cls_preds': point_cls_preds,
-                                 'point_reg_preds': point_reg_preds, 'point_box_preds': boxes}
+                                 'point_reg_preds': point_reg_preds, 'point_box_preds': boxes,
+                                 'point_pooled_features': pooled}        # a reference: prepare_loss(towers=True) starts here
         return batch_dict
 
     # ---- target assignment (point_head_box6d_vote.py:171-326, :387-407) ------------------------------------------------
@@ -345,20 +354,36 @@ class PointHeadBox6DVote(nn.Module):
         spec, tensors = self._loss_inputs()
         return head_loss.forward(spec, *(t.detach().contiguous() for t in tensors), per_point=True)
 
-    def prepare_loss(self, batch_dict, requires_grad=False):
+    def prepare_loss(self, batch_dict, requires_grad=False, towers=False):
         """Fills forward_ret_dict with what the reference's training forward puts there (:823-876), for the batch_dict an eval
         forward returned plus batch_dict['gt_boxes'] (B, M, 9 + 1): the five labels of assign_training_targets,
         point_candidate_coords and point_vote_coords as (N, 3), beside the predictions forward() left.
         requires_grad=True makes point_vote_coords, point_cls_preds and point_reg_preds leaves, so that get_loss()[0].backward()
-        leaves dL/d(prediction) in their .grad."""
+        leaves dL/d(prediction) in their .grad.
+        towers=True re-evaluates shared_fc_layer, cls_layers and reg_layers from point_pooled_features (made a leaf) with a graph
+        to their parameters and stores those predictions — the bits of the eval forward — in place of the leaves: backward()
+        then leaves .grad on every parameter of the three stacks and on point_pooled_features; point_vote_coords stays a
+        leaf, vote_layers and the backbone get nothing (see the module docstring)."""
         ret = self.forward_ret_dict
         if ret is None or 'point_reg_preds' not in ret:
             raise RuntimeError("prepare_loss needs the forward_ret_dict of an eval forward")
+        if towers and self.training:
+            raise RuntimeError("the HIP head folds BatchNorm: call .eval() first")
         ret.update(self.assign_training_targets(batch_dict))
         ret['point_candidate_coords'] = batch_dict['point_candidate_coords'][:, 1:4].contiguous()
         ret['point_vote_coords'] = batch_dict['point_vote_coords'][:, 1:4].contiguous()
         for key in ('point_vote_coords', 'point_cls_preds', 'point_reg_preds'):
             ret[key] = ret[key].detach().requires_grad_(requires_grad)
+        if towers:
+            pooled = ret['point_pooled_features'].detach().requires_grad_(requires_grad)
+            ret['point_pooled_features'] = pooled
+            f = self._prepare(pooled.device)
+            k0 = sum(seq[-3].out_channels for seq in self.SA_module.mlps)
+            with torch.set_grad_enabled(requires_grad):
+                chains = [mlp_backward.folded_params(seq, f[key]) for seq, key in
+                          ((self.shared_fc_layer, 'shared'), (self.cls_layers, 'cls'), (self.reg_layers, 'reg'))]
+                cls, reg = mlp_backward.folded_chain(pooled.view(-1, pooled.shape[-1]), chains[0], chains[1:], k0=k0)
+            ret['point_cls_preds'], ret['point_reg_preds'] = cls, reg
         return ret
 
     def get_vote_layer_loss(self, tb_dict=None):

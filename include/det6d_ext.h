@@ -188,6 +188,51 @@ int det6d_ext_centerness_labels(int n, const float *points, const float *box_lab
 int det6d_ext_corner_loss(int n, const float *pred_boxes, int ld_pred, const float *gt_boxes, int ld_gt, float *loss,
                           det6d_stream_t stream);
 
+/* ------------------------------------------------------------------ MLP backward ------- */
+
+/* The backward pass of one pointwise layer z = x W + shift as det6d_linear computes it (BatchNorm folded: W (k, n) row-major,
+ * the layer's input x (rows, k), its pre-activation output z (rows, n)), given dz = dL/dz:
+ *   dx[r][c]  = sum_j dz[r][j] * w[wrow0 + c][j]          (rows, k)   the gradient of the layer's input
+ *   dw[c][j]  = sum_r x[r][xcol0 + c] * dz[r][j]          (k, n)      the gradient of the folded weights
+ *   dshift[j] = sum_r dz[r][j]                            (n)         the gradient of the folded shift
+ * A tower is one call per layer, from the last layer to the first: the last layer has no activation, so its dz is the loss
+ * gradient; with RELU_INPUT the dx of a call is already the dz of the layer before (x is that layer's ReLU output); the second
+ * of two towers that read the same input adds its dx into the first one's with ACCUMULATE_DX.  No dz is materialised apart.
+ * Executable model: tests/models/mlp_backward.py.
+ * Arithmetic (a pure function of the inputs: no floating-point atomics, nothing depends on the grid, the number of CUs or the
+ * order in which workgroups arrive):
+ *   dx[r][c]: ONE fp32 accumulator from 0, the products in ascending j, each step an fma — the chain v_mfma_f32_32x32x2_f32
+ *     gives (csrc/mfma_tile.h); then, with RELU_INPUT, dx = x[r][xcol0 + c] > 0 ? dx : 0 (a NaN in x compares false: 0); then,
+ *     with ACCUMULATE_DX, dx = dx_before + dx, one add.
+ *   dw[c][j]: the rows are cut into slabs of DET6D_EXT_LINEAR_BACKWARD_SLAB rows (the last one may be short); a slab's partial
+ *     is the fma chain from 0 over its rows in ascending order; dw = (partial_0 + partial_1) + partial_2 ..., fp32 adds in
+ *     ascending slab order.  dw is written, not accumulated.
+ *   dshift[j]: the same slabs, a partial being the chain of fp32 adds from 0 over its rows; the same order over the slabs.
+ * rows == 0: with neither dw nor dshift nothing is launched (dx has no rows; ACCUMULATE_DX leaves it alone); otherwise ONE fill
+ * kernel (the slab-sum kernel over zero slabs, no memset: the padding of dw's rows is not touched) writes dw and dshift as zeros.
+ * x and w follow the rules det6d_linear enforces for its a and w: ldx % 4 == 0, ldw % 4 == 0, both pointers 16-byte aligned,
+ * xcol0 + k <= ldx, n <= ldw; dz, dx, dw, dshift take what det6d_linear's output takes: any 4-byte aligned pointer, n <= lddz,
+ * dxcol0 + k <= lddx, n <= lddw.  x is read (and checked) only for dw and for RELU_INPUT, w only for dx.  Columns outside
+ * [dxcol0, dxcol0 + k) of dx and [0, n) of dw are left alone.  dx must not overlap the inputs.
+ * Limits: 0 <= rows <= 2^24, 1 <= k, n <= 4096, 0 <= xcol0, 0 <= dxcol0, 0 <= wrow0 <= 2^24, flags in [0, 3], at least one of
+ * dx / dw / dshift, ACCUMULATE_DX only with dx, workspace_bytes >= det6d_ext_linear_backward_workspace_bytes(rows, k, n) when
+ * dw or dshift is asked for (0 for a single slab: its partial is the result; else one (k, n) + (n) block per slab). */
+enum { DET6D_EXT_LINEAR_BACKWARD_SLAB = 256 };
+enum { DET6D_EXT_LINEAR_BACKWARD_RELU_INPUT = 1, DET6D_EXT_LINEAR_BACKWARD_ACCUMULATE_DX = 2 };      /* flags */
+long long det6d_ext_linear_backward_workspace_bytes(int rows, int k, int n);
+int det6d_ext_linear_backward(int rows, int k, int n,
+        const float *x,  int ldx,  int xcol0,   /* the layer's input: columns [xcol0, xcol0 + k) of (rows, ldx)        */
+        const float *w,  int ldw,  int wrow0,   /* folded weights as det6d_linear reads them: rows [wrow0, wrow0 + k),  */
+                                                /* columns [0, n) of a row-major (.., ldw) matrix                       */
+        const float *dz, int lddz,              /* (rows, n): gradient w.r.t. the layer's PRE-activation output         */
+        int flags,                              /* 1 RELU_INPUT: dx[r][c] = x[r][c] > 0 ? dx[r][c] : 0  (x is itself a  */
+                                                /*   ReLU output, so dx is the previous layer's dz)                      */
+                                                /* 2 ACCUMULATE_DX: dx = dx_before + (masked) result, one add/element    */
+        float *dx, int lddx, int dxcol0,        /* (rows, k) or NULL                                                    */
+        float *dw, int lddw,                    /* (k, n), written not accumulated, or NULL                             */
+        float *dshift,                          /* (n) column sums of dz, or NULL                                       */
+        void *workspace, long long workspace_bytes, det6d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

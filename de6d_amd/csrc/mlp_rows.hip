@@ -642,7 +642,7 @@ DET6D_API int det6d_mlp_rows_supported(int nchains, const int *nlayers, const de
 DET6D_API int det6d_mlp_rows(int rows, const float *x, int ldx, int xcol0, int nchains, const int *nlayers,
                              const det6d_rows_layer *layers, det6d_stream_t stream) {
   D6_GEMM_PRIO_HOST();
-  if (rows < 0 || !x || ldx <= 0 || xcol0 < 0) return DET6D_EINVAL;
+  if (rows < 0 || (!x && rows > 0) || ldx <= 0 || xcol0 < 0) return DET6D_EINVAL;     // (no rows: an empty tensor has no address)
   RowsArgs g;
   if (rows_plan(nchains, nlayers, layers, g) != DET6D_OK) return DET6D_EINVAL;
   g.rows = rows; g.x = x; g.ldx = ldx; g.xcol0 = xcol0;
@@ -689,7 +689,9 @@ DET6D_API int det6d_mlp_rows(int rows, const float *x, int ldx, int xcol0, int n
     for (int l = 0; l < nlayers[c]; ++l) max_tiles = max_tiles > (layers[o + l].n + 31) / 32 ? max_tiles : (layers[o + l].n + 31) / 32;
   // DET6D_ROWS_RB: 2 (default) = 64-row tiles for narrow stacks over >= 16384 rows, 3 = over any number of rows, 1 = never
   static const int rb_env = det6d_env_int("DET6D_ROWS_RB", 2);
-  const int rb = (rb_env >= 2 && g.kchunk == g.k0 && max_tiles <= 2 && (rows >= 16384 || rb_env == 3)) ? 2 : 1;
+  // (a 64-row tile of a narrow stack with a long input, e.g. [640 -> 64 -> 3], does not fit the CU: rows_plan promised 32-row tiles)
+  const bool fits64 = sizeof(float) * 64 * ((size_t)(g.wa + 1) + (size_t)(g.wb + 1)) <= 160 * 1024;
+  const int rb = (rb_env >= 2 && g.kchunk == g.k0 && max_tiles <= 2 && fits64 && (rows >= 16384 || rb_env == 3)) ? 2 : 1;
   const size_t lds_bytes = sizeof(float) * 32 * rb * ((size_t)(g.wa + 1) + (size_t)(g.wb + 1));
   if (lds_bytes > 160 * 1024) return DET6D_EINVAL;
   // (the need varies per call: the limit is set once per device, to the CU's 160 KB)

@@ -280,6 +280,28 @@ def test_mlp_rows_supported_query_mirrors_the_launch_checks():
     assert not fused.mlp_rows_eligible(256, [[(z(256, 128), 0, None, 256, 128, 1, None, 0)]])    # last layer without an output
     assert not fused.mlp_rows_eligible(256, ok + ok + ok)                                           # three chains
 
+    def stack(k0, *widths):
+        ks = (k0,) + widths[:-1]
+        last = len(widths) - 1
+        return [(z(k, n), 0, None, k, n, int(i < last), z(4, n) if i == last else None, 0) for i, (k, n) in enumerate(zip(ks, widths))]
+    # the LDS boundary: 32 x (993 + 257) x 4 = 160 000 bytes fit, 32 x (1025 + 257) x 4 = 164 096 do not
+    assert fused.mlp_rows_eligible(992, [stack(992, 256, 32)])
+    assert not fused.mlp_rows_eligible(1024, [stack(1024, 256, 32)])
+    assert not fused.mlp_rows_eligible(64, [stack(64, 64, 64, 64, 64, 5)])                          # five layers
+    assert not fused.mlp_rows_eligible(100, [stack(100, 64, 3)])                                    # k % 32
+    assert not fused.mlp_rows_eligible(512, [stack(512, 128, 3), stack(480, 128, 32)])              # two chains, two input widths
+    assert not L_supported(fused, [stack(512, 128, 3), stack(480, 128, 32)])
+    # every stack tests/test_mlp_rows_gpu.py launches (its group 1) is one the library accepts
+    from tests.test_mlp_rows_gpu import STACKS
+    for name, chains in STACKS.items():
+        assert fused.mlp_rows_eligible(chains[0][0], [stack(k0, *widths) for k0, widths, _ in chains]), name
+
+
+def L_supported(fused, chains):
+    """det6d_mlp_rows_supported itself (mlp_rows_eligible refuses chains of different k0 before it asks the library)"""
+    _, counts, arr = fused._rows_descriptors(chains)
+    return bool(fused.L.lib().det6d_mlp_rows_supported(len(chains), counts, arr))
+
 
 def test_bench_refuses_more_ranks_than_devices():
     """`bench.py --gpus N` with fewer than N visible devices exits non-zero BEFORE any rank is started or any rendezvous is

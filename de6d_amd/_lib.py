@@ -48,6 +48,18 @@ class RowsLayer(ctypes.Structure):
                 ("out", c_void_p), ("ldo", c_int), ("ocol0", c_int)]
 
 
+class LaunchPlan(ctypes.Structure):
+    """det6d_launch_plan (include/det6d_ops.h): what a det6d_*_plan query fills; the route enums are in the header"""
+    _fields_ = [("route", c_int), ("grid_x", c_int), ("grid_y", c_int), ("block", c_int), ("lds_bytes", ctypes.c_uint),
+                ("tile_rows", c_int)]
+
+
+#: route numbers of det6d_launch_plan.route by entry point (the enums of include/det6d_ops.h)
+ROWS_ROUTES = ("W", "R", "G1", "GC", "G2")
+CHAIN_ROUTES = ("WIDE", "REG", "LDS")
+GROUP_ROUTES = ("STREAM", "ONEPASS4", "ONEPASS8")
+
+
 class EvalMatchArgs(ctypes.Structure):
     """det6d_eval_match_args (include/det6d_ops.h)"""
     _fields_ = [("n_frames", ctypes.c_int), ("n_thresh", ctypes.c_int), ("metric", ctypes.c_int),
@@ -100,6 +112,10 @@ _SIGNATURES = {
                                           _P, c_int, c_int, _P, c_int, _P],
     "det6d_compact_groups": [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P],
     "det6d_mlp_group3_supported": [c_int, c_int, c_int, c_int, c_int],
+    "det6d_mlp_group3_plan": [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(LaunchPlan)],
+    "det6d_mlp_chain3_plan": [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(LaunchPlan)],
+    "det6d_mlp_rows_plan": [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(RowsLayer),
+                            ctypes.POINTER(LaunchPlan)],
     "det6d_mlp_group3": [c_int, _P, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int,
                          _P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int, _P],
     "det6d_mlp_rows": [c_int, _P, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(RowsLayer), _P],

@@ -23,6 +23,7 @@ static inline int det6d_check_launch(const char *what) {
 }
 
 static inline int det6d_divup(int a, int b) { return (a + b - 1) / b; }
+static inline int det6d_min(int a, int b) { return a < b ? a : b; }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE property of a kernel: set it once per (call site, device) — a
 // process-wide "done" flag would leave a second device of the process at the default limit.  The race of two host threads on
@@ -36,6 +37,20 @@ static inline int det6d_divup(int a, int b) { return (a + b - 1) / b; }
       d6_attr_dev_ = d6_dev_;                                                                                       \
     }                                                                                                               \
   } while (0)
+
+// Launches KERNEL(g) as a launch plan says (include/det6d_ops.h: det6d_launch_plan, made by the entry point's plan function).
+// lds_limit: the kernel's dynamic-LDS limit, set first; by default what the plan asks for (a kernel whose need is fixed by its
+// template arguments), nothing when that is 0.
+template <auto KERNEL, typename Args>
+static inline int det6d_launch(const Args &g, const det6d_launch_plan &p, hipStream_t stream, const char *what, size_t lds_limit) {
+  if (lds_limit) DET6D_MAX_DYNAMIC_LDS(KERNEL, lds_limit);
+  hipLaunchKernelGGL(KERNEL, dim3(p.grid_x, p.grid_y), dim3(p.block), p.lds_bytes, stream, g);
+  return det6d_check_launch(what);
+}
+template <auto KERNEL, typename Args>
+static inline int det6d_launch(const Args &g, const det6d_launch_plan &p, hipStream_t stream, const char *what) {
+  return det6d_launch<KERNEL>(g, p, stream, what, p.lds_bytes);
+}
 
 // Environment switches.  Two kinds:
 //  * det6d_switch_*: read by the SHIPPED library: DET6D_FPS_COOP_FAST (fps_coop.hip) and nothing else (DET6D_DENSE_ROWS is

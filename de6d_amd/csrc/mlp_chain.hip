@@ -687,6 +687,9 @@ __global__ __launch_bounds__(512) void mlp_chain_wide_kernel(const ChainArgs g) 
 
 // ---- host side ----
 
+// dynamic LDS of mlp_chain_wide_kernel<C2, ..>
+constexpr size_t chain_wide_lds_bytes(int c2) { return sizeof(float) * ((size_t)70 * 64 + (size_t)66 * c2 + (size_t)c2 * 128); }
+
 // dense rows: idx / cnt and (n, m, ns), no list; compact rows: the list (hdr, crow_p, crow_c), rows = its capacity, the rest 0
 static ChainArgs chain_args(int rows, int n, int m, int ns, const float *a, int lda, const int *idx, const float *ctr, int ldctr,
                             const int *cnt, const float *w1, int ldw1, const float *s1, int c1, const float *w2, int ldw2,
@@ -696,64 +699,83 @@ static ChainArgs chain_args(int rows, int n, int m, int ns, const float *a, int 
                    y, ldy, col0, hdr, crow_p, crow_c};   // the struct's field order
 }
 
-// the wide kernel: one 512-thread workgroup per CU (the weights fill most of its LDS), two waves per SIMD
-template <int C2, int NS, bool COMPACT>
-static void launch_wide(const ChainArgs &g, hipStream_t stream) {
-  const size_t lds_bytes = sizeof(float) * ((size_t)70 * 64 + (size_t)66 * C2 + (size_t)C2 * 128);
-  const int ntiles = g.rows / 32;
-  const int wb = det6d_divup(ntiles, 8) < 256 ? det6d_divup(ntiles, 8) : 256;
-  DET6D_MAX_DYNAMIC_LDS((mlp_chain_wide_kernel<C2, NS, COMPACT>), lds_bytes);
-  hipLaunchKernelGGL((mlp_chain_wide_kernel<C2, NS, COMPACT>), dim3(wb), dim3(512), lds_bytes, stream, g);
+// The plan of det6d_mlp_chain3 (dense rows: b scenes x m centres x ns rows) and det6d_mlp_chain3_compact (a row list of
+// `capacity` rows; ns, b, m unused): refusal, or the route and its launch geometry.  b == 0 asks about the widths alone.
+// a_aligned16: the point rows' address; w_aligned16: w1..w3, s1, s2 and ldw1..3 * 4 are multiples of 16 bytes.
+static int chain_plan(int lda, int c1, int c2, int c3, int ns, int b, int m, bool compact, int capacity, bool a_aligned16,
+                      bool w_aligned16, det6d_launch_plan &p) {
+  if (compact ? (b && (capacity <= 0 || (capacity & 127))) : ((ns != 16 && ns != 32) || b < 0 || (b && m <= 0))) return DET6D_EINVAL;
+  const long long rows = compact ? (b ? capacity : 0) : (long long)b * m * ns;
+  if (rows % 32 || rows > 0x7fffffff) return DET6D_EINVAL;
+  // a 32-row tile of ns = 16 rows holds two centres, which must be of ONE scene
+  const bool pairs_ok = compact || !b || ns == 32 || !(m & 1);
+  static const bool no_wide = det6d_env_set("DET6D_CHAIN_NO_WIDE"), use_lds_env = det6d_env_set("DET6D_CHAIN_LDS");
+  const bool wide = lda == 68 && c1 == 64 && (c2 == 64 || c2 == 96) && c3 == 128 && pairs_ok && w_aligned16 && !no_wide;
+  const bool reg = lda == 4 && ((c1 == 16 && c2 == 16 && c3 == 32) || (c1 == 32 && c2 == 32 && c3 == 64)) && (compact || (pairs_ok && !use_lds_env));
+  const int ntiles = (int)(rows / 32);
+  if (wide) {
+    // one 512-thread workgroup per CU (the weights fill most of its LDS), two waves per SIMD
+    p = det6d_launch_plan{DET6D_CHAIN_WIDE, det6d_min(det6d_divup(ntiles, 8), 256), 1, 512, (unsigned)chain_wide_lds_bytes(c2), 32};
+    return DET6D_OK;
+  }
+  if (lda < 4 || lda > kMaxK1 || (lda & 3) || !a_aligned16 || (compact && !reg)) return DET6D_EINVAL;
+  if (c1 <= 0 || c1 > kMaxC || c2 <= 0 || c2 > kMaxC || c3 <= 0 || c3 > kMaxC3) return DET6D_EINVAL;
+  // four waves, a tile each.  LDS kernel: persistent-ish (256 * 6 workgroups amortise the weight staging over many tiles).
+  // Register kernel, dense: a grid of exactly one residency round (256 CUs x 4 SIMDs x 4 waves) so that every wave walks the
+  // same number of tiles (1536 blocks left half the chip idle in the second round); compact: up to 2048 workgroups, each wave
+  // walks ceil(live tiles / waves) tiles (measured on 32-scene passes, SA1's wide group alone / with the chip full: 768
+  // workgroups 137 / 65 us, 1024: 115 / 64, 2048: 97 / 65, 4096: 87 / 70; ray-cast scenes 578 / 205, 507 / 205, 366 / 201,
+  // 299 / 206).  DET6D_CHAIN_BLOCKS: experiments build only.
+  static const int reg_cap_dense = det6d_env_int("DET6D_CHAIN_BLOCKS", 1024), reg_cap_compact = det6d_env_int("DET6D_CHAIN_BLOCKS", 2048);
+  const int cap = !reg ? 256 * 6 : compact ? reg_cap_compact : det6d_min(256 * 6, reg_cap_dense);
+  p = det6d_launch_plan{reg ? DET6D_CHAIN_REG : DET6D_CHAIN_LDS, det6d_min(det6d_divup(ntiles, kChainWaves), cap), 1, 64 * kChainWaves, 0, 32};
+  return DET6D_OK;
+}
+
+DET6D_API int det6d_mlp_chain3_plan(int lda, int c1, int c2, int c3, int ns, int b, int m, int compact, int capacity,
+                                    det6d_launch_plan *plan) {
+  return plan ? chain_plan(lda, c1, c2, c3, ns, b, m, compact != 0, capacity, true, true, *plan) : DET6D_EINVAL;
+}
+
+// Both entries from here: leading dimensions, the plan, the instance of (route, second width, ns, compact).  A case label
+// carries its instance's template arguments (compact lists: NS = 32; the LDS kernel: run-time widths).
+constexpr int chain_key(int route, int c2, int ns, bool compact) { return ((route * 128 + c2) * 64 + ns) * 2 + compact; }
+static int chain_run(const ChainArgs &g, int b, bool compact, hipStream_t s, const char *what) {
+  if (g.ldctr < 3 || g.ldw1 < g.c1 || g.ldw2 < g.c2 || g.ldw3 < g.c3) return DET6D_EINVAL;
+  const bool w_aligned16 = !((g.ldw1 | g.ldw2 | g.ldw3) & 3) &&
+                           !(((uintptr_t)g.w1 | (uintptr_t)g.w2 | (uintptr_t)g.w3 | (uintptr_t)g.s1 | (uintptr_t)g.s2) & 15);
+  det6d_launch_plan p;
+  if (chain_plan(g.lda, g.c1, g.c2, g.c3, g.ns, b, g.m, compact, g.rows, !((uintptr_t)g.a & 15), w_aligned16, p) != DET6D_OK) return DET6D_EINVAL;
+  if (g.rows == 0) return DET6D_OK;
+  const bool lds = p.route == DET6D_CHAIN_LDS;
+  switch (chain_key(p.route, lds ? 0 : g.c2, lds ? 0 : compact ? 32 : g.ns, compact)) {
+    case chain_key(DET6D_CHAIN_WIDE, 64, 16, false): return det6d_launch<mlp_chain_wide_kernel<64, 16, false>>(g, p, s, what);
+    case chain_key(DET6D_CHAIN_WIDE, 64, 32, false): return det6d_launch<mlp_chain_wide_kernel<64, 32, false>>(g, p, s, what);
+    case chain_key(DET6D_CHAIN_WIDE, 96, 16, false): return det6d_launch<mlp_chain_wide_kernel<96, 16, false>>(g, p, s, what);
+    case chain_key(DET6D_CHAIN_WIDE, 96, 32, false): return det6d_launch<mlp_chain_wide_kernel<96, 32, false>>(g, p, s, what);
+    case chain_key(DET6D_CHAIN_WIDE, 64, 32, true): return det6d_launch<mlp_chain_wide_kernel<64, 32, true>>(g, p, s, what);
+    case chain_key(DET6D_CHAIN_WIDE, 96, 32, true): return det6d_launch<mlp_chain_wide_kernel<96, 32, true>>(g, p, s, what);
+    case chain_key(DET6D_CHAIN_REG, 16, 16, false): return det6d_launch<mlp_chain_reg_kernel<16, 16, 32, 16>>(g, p, s, what);
+    case chain_key(DET6D_CHAIN_REG, 16, 32, false): return det6d_launch<mlp_chain_reg_kernel<16, 16, 32, 32>>(g, p, s, what);
+    case chain_key(DET6D_CHAIN_REG, 32, 16, false): return det6d_launch<mlp_chain_reg_kernel<32, 32, 64, 16>>(g, p, s, what);
+    case chain_key(DET6D_CHAIN_REG, 32, 32, false): return det6d_launch<mlp_chain_reg_kernel<32, 32, 64, 32>>(g, p, s, what);
+    case chain_key(DET6D_CHAIN_REG, 16, 32, true): return det6d_launch<mlp_chain_reg_kernel<16, 16, 32, 32, true>>(g, p, s, what);
+    case chain_key(DET6D_CHAIN_REG, 32, 32, true): return det6d_launch<mlp_chain_reg_kernel<32, 32, 64, 32, true>>(g, p, s, what);
+    case chain_key(DET6D_CHAIN_LDS, 0, 0, false): return det6d_launch<mlp_chain_kernel>(g, p, s, what);
+    default: return DET6D_EINVAL;      // unreachable: chain_plan names no other (route, widths, ns, compact)
+  }
 }
 
 DET6D_API int det6d_mlp_chain3(int rows, int n, int m, int ns, const float *a, int lda, const int *idx,
-                               const float *ctr, int ldctr, const int *cnt, const float *w1, int ldw1,
-                               const float *s1, int c1, const float *w2, int ldw2, const float *s2, int c2,
-                               const float *w3, int ldw3, const float *s3, int c3, float *y, int ldy, int col0,
-                               det6d_stream_t stream) {
+                               const float *ctr, int ldctr, const int *cnt, const float *w1, int ldw1, const float *s1,
+                               int c1, const float *w2, int ldw2, const float *s2, int c2, const float *w3, int ldw3,
+                               const float *s3, int c3, float *y, int ldy, int col0, det6d_stream_t stream) {
   D6_GEMM_PRIO_HOST();
-  if (rows < 0 || n <= 0 || m <= 0 || (ns != 16 && ns != 32) || !a || !idx || !ctr || !cnt || !w1 || !w2 || !w3 ||
-      !s1 || !s2 || !s3 || !y)
+  if (rows < 0 || n <= 0 || m <= 0 || (ns != 16 && ns != 32) || !a || !idx || !ctr || !cnt || !w1 || !w2 || !w3 || !s1 || !s2 ||
+      !s3 || !y || rows % (m * ns))
     return DET6D_EINVAL;
-  const bool wide = lda == 68 && c1 == 64 && (c2 == 64 || c2 == 96) && c3 == 128 && (ns == 32 || !(m & 1)) && !(ldw1 & 3) &&
-                    !(ldw2 & 3) && !(ldw3 & 3) &&
-                    !(((uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)w3 | (uintptr_t)s1 | (uintptr_t)s2) & 15) &&
-                    !det6d_env_set("DET6D_CHAIN_NO_WIDE");
-  if (!wide) {
-    if (lda < 4 || lda > kMaxK1 || (lda & 3) || ((uintptr_t)a & 15) || ldctr < 3) return DET6D_EINVAL;
-    if (c1 <= 0 || c1 > kMaxC || c2 <= 0 || c2 > kMaxC || c3 <= 0 || c3 > kMaxC3) return DET6D_EINVAL;
-  }
-  if (ldw1 < c1 || ldw2 < c2 || ldw3 < c3 || rows % (m * ns) || rows % 32) return DET6D_EINVAL;
-  if (rows == 0) return DET6D_OK;
-  const ChainArgs g = chain_args(rows, n, m, ns, a, lda, idx, ctr, ldctr, cnt, w1, ldw1, s1, c1, w2, ldw2, s2, c2, w3, ldw3, s3, c3, y,
-                                 ldy, col0, nullptr, nullptr, nullptr);
-  const int ntiles = rows / 32;
-  if (wide) {
-    if (c2 == 64 && ns == 16) launch_wide<64, 16, false>(g, (hipStream_t)stream);
-    else if (c2 == 64) launch_wide<64, 32, false>(g, (hipStream_t)stream);
-    else if (ns == 16) launch_wide<96, 16, false>(g, (hipStream_t)stream);
-    else launch_wide<96, 32, false>(g, (hipStream_t)stream);
-    return det6d_check_launch("det6d_mlp_chain3");
-  }
-  int blocks = det6d_divup(ntiles, kChainWaves);
-  if (blocks > 256 * 6) blocks = 256 * 6;     // persistent-ish: amortise the weight staging over many tiles
-  static const bool use_lds_env = det6d_env_set("DET6D_CHAIN_LDS");
-  const bool use_lds = use_lds_env || (ns == 16 && (m & 1));   // the register kernel pairs two centres of ONE batch per tile
-  // register kernel: a grid of exactly one residency round (256 CUs x 4 SIMDs x 4 waves) so that every wave
-  // walks the same number of tiles (1536 blocks left half the chip idle in the second round)
-  static const int reg_blocks_env = det6d_env_int("DET6D_CHAIN_BLOCKS", 1024);
-  const int reg_blocks = blocks < reg_blocks_env ? blocks : reg_blocks_env;
-  if (!use_lds && lda == 4 && c1 == 16 && c2 == 16 && c3 == 32 && ns == 16)
-    hipLaunchKernelGGL((mlp_chain_reg_kernel<16, 16, 32, 16>), dim3(reg_blocks), dim3(256), 0, (hipStream_t)stream, g);
-  else if (!use_lds && lda == 4 && c1 == 16 && c2 == 16 && c3 == 32 && ns == 32)
-    hipLaunchKernelGGL((mlp_chain_reg_kernel<16, 16, 32, 32>), dim3(reg_blocks), dim3(256), 0, (hipStream_t)stream, g);
-  else if (!use_lds && lda == 4 && c1 == 32 && c2 == 32 && c3 == 64 && ns == 16)
-    hipLaunchKernelGGL((mlp_chain_reg_kernel<32, 32, 64, 16>), dim3(reg_blocks), dim3(256), 0, (hipStream_t)stream, g);
-  else if (!use_lds && lda == 4 && c1 == 32 && c2 == 32 && c3 == 64 && ns == 32)
-    hipLaunchKernelGGL((mlp_chain_reg_kernel<32, 32, 64, 32>), dim3(reg_blocks), dim3(256), 0, (hipStream_t)stream, g);
-  else
-    hipLaunchKernelGGL(mlp_chain_kernel, dim3(blocks), dim3(64 * kChainWaves), 0, (hipStream_t)stream, g);
-  return det6d_check_launch("det6d_mlp_chain3");
+  return chain_run(chain_args(rows, n, m, ns, a, lda, idx, ctr, ldctr, cnt, w1, ldw1, s1, c1, w2, ldw2, s2, c2, w3, ldw3, s3, c3, y, ldy,
+                              col0, nullptr, nullptr, nullptr), rows / (m * ns), false, (hipStream_t)stream, "det6d_mlp_chain3");
 }
 
 // The same chains over a compact (ragged) row list: rows, classes and output centres come from det6d_compact_groups
@@ -763,31 +785,7 @@ DET6D_API int det6d_mlp_chain3_compact(int capacity, const int *hdr, const int *
                                        int c1, const float *w2, int ldw2, const float *s2, int c2, const float *w3, int ldw3,
                                        const float *s3, int c3, float *y, int ldy, int col0, det6d_stream_t stream) {
   D6_GEMM_PRIO_HOST();
-  if (capacity <= 0 || (capacity & 127) || !hdr || !crow_p || !crow_c || !a || !ctr || ldctr < 3 || !w1 || !w2 || !w3 || !s1 ||
-      !s2 || !s3 || !y)
-    return DET6D_EINVAL;
-  if (ldw1 < c1 || ldw2 < c2 || ldw3 < c3) return DET6D_EINVAL;
-  const bool wide = lda == 68 && c1 == 64 && (c2 == 64 || c2 == 96) && c3 == 128 && !(ldw1 & 3) && !(ldw2 & 3) && !(ldw3 & 3) &&
-                    !(((uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)w3 | (uintptr_t)s1 | (uintptr_t)s2) & 15);
-  const bool narrow = lda == 4 && !((uintptr_t)a & 15) && ((c1 == 16 && c2 == 16 && c3 == 32) || (c1 == 32 && c2 == 32 && c3 == 64));
-  if (!wide && !narrow) return DET6D_EINVAL;
-  const ChainArgs g = chain_args(capacity, 0, 0, 0, a, lda, nullptr, ctr, ldctr, nullptr, w1, ldw1, s1, c1, w2, ldw2, s2, c2, w3, ldw3,
-                                 s3, c3, y, ldy, col0, hdr, crow_p, crow_c);
-  const int ntiles = capacity / 32;
-  if (wide) {
-    if (c2 == 64) launch_wide<64, 32, true>(g, (hipStream_t)stream);
-    else launch_wide<96, 32, true>(g, (hipStream_t)stream);
-    return det6d_check_launch("det6d_mlp_chain3_compact");
-  }
-  // grid: up to 2048 workgroups, each wave walks ceil(live tiles / waves) tiles (measured on 32-scene passes, SA1's wide
-  // group alone / with the chip full: 768 workgroups 137 / 65 us, 1024: 115 / 64, 2048: 97 / 65, 4096: 87 / 70; ray-cast
-  // scenes 578 / 205, 507 / 205, 366 / 201, 299 / 206)
-  int blocks = det6d_divup(ntiles, 4);
-  static const int cap = det6d_env_int("DET6D_CHAIN_BLOCKS", 2048);   // experiments build only
-  if (blocks > cap) blocks = cap;
-  if (c1 == 16)
-    hipLaunchKernelGGL((mlp_chain_reg_kernel<16, 16, 32, 32, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, g);
-  else
-    hipLaunchKernelGGL((mlp_chain_reg_kernel<32, 32, 64, 32, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, g);
-  return det6d_check_launch("det6d_mlp_chain3_compact");
+  if (!hdr || !crow_p || !crow_c || !a || !ctr || !w1 || !w2 || !w3 || !s1 || !s2 || !s3 || !y) return DET6D_EINVAL;
+  return chain_run(chain_args(capacity, 0, 0, 0, a, lda, nullptr, ctr, ldctr, nullptr, w1, ldw1, s1, c1, w2, ldw2, s2, c2, w3, ldw3, s3,
+                              c3, y, ldy, col0, hdr, crow_p, crow_c), 1, true, (hipStream_t)stream, "det6d_mlp_chain3_compact");
 }

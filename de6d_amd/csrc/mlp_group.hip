@@ -84,7 +84,8 @@ __device__ __forceinline__ void g_leave(int *ticket, int workers) {
 // Column owned by (accumulator tile j, lane l31) inside a wave's C/4-wide quarter: VW = min(TN, 4) consecutive columns
 // per lane so that ONE buffer_load_dwordx{VW} brings the B operands of VW tiles (any assignment of columns to
 // (tile, lane) is a valid GEMM; the epilogues use the same map).
-template <int TN> constexpr int kGroupVW = TN >= 4 ? 4 : TN;
+constexpr int group_vw(int tn) { return tn >= 4 ? 4 : tn; }
+template <int TN> constexpr int kGroupVW = group_vw(TN);
 template <int TN>
 __device__ __forceinline__ int tile_col(int j, int l31) {
   constexpr int VW = kGroupVW<TN>;
@@ -579,7 +580,8 @@ __device__ __forceinline__ void stream_layer(const float *__restrict__ X, const 
 // costs no residency: the head's groups (C1 = 256) hold 66 KB, two workgroups per CU with or without the 4 KB.  SA3's wide
 // group in this form (C1 = 128, DET6D_GROUP_STREAM bit 4) fits three workgroups in the CU's 160 KB with 2 KB to spare and keeps
 // reading them from the cache, in the gather's batch.
-template <int C1> constexpr bool kStreamStagesW1 = C1 >= 256;
+constexpr bool stream_stages_w1(int c1) { return c1 >= 256; }
+template <int C1> constexpr bool kStreamStagesW1 = stream_stages_w1(C1);
 
 template <int C1, int C2, int C3, bool COMPACT>
 __global__ __launch_bounds__(256, 2) void mlp_group_stream_kernel(const GroupArgs g) {
@@ -668,48 +670,49 @@ __global__ __launch_bounds__(256, 2) void mlp_group_stream_kernel(const GroupArg
   if (ticket && tid == 0) g_leave(ticket, min((int)gridDim.x, live_tiles));
 }
 
-// persistent grid: as many workgroups as the chip holds at a time by their LDS (256 CUs x at most max_per_cu), one 32-row
-// tile each at the least
-static int group_grid(int rows, size_t lds_bytes, int max_per_cu) {
-  int per_cu = (int)((160 * 1024) / lds_bytes);
-  per_cu = per_cu < 1 ? 1 : (per_cu > max_per_cu ? max_per_cu : per_cu);
-  const int blocks = rows / 32;
-  return blocks > 256 * per_cu ? 256 * per_cu : blocks;
+// dynamic LDS of the two kernels: the activation buffers + tags + store scratch (+ W1 rows and shift) + drawn tiles
+constexpr size_t group_stream_lds_bytes(int c1, int c3) {
+  return sizeof(float) * (32 * (size_t)(c1 + 1 + 2 * 129) + 64 + 4 * 64 * group_vw(c3 / 128) + (stream_stages_w1(c1) ? 4 * c1 : 0) + 4);
+}
+constexpr size_t group_lds_bytes(int c1, int c2, int c3, int nw) {
+  return sizeof(float) * (32 * (size_t)(c1 + 1 + c2 + 1) + 64 + nw * 64 * group_vw(c3 / (32 * nw)) + 4);
 }
 
-template <int C1, int C2, int C3, bool COMPACT>
-int launch_group_stream(const GroupArgs &g, hipStream_t stream) {
-  const size_t lds_bytes = sizeof(float) * (32 * (size_t)(C1 + 1 + 2 * 129) + 64 + 4 * 64 * kGroupVW<C3 / 128> +   // + tags + store scratch
-                                            (kStreamStagesW1<C1> ? 4 * C1 : 0) + 4);                                // + W1 rows and shift + drawn tiles
-  DET6D_MAX_DYNAMIC_LDS((mlp_group_stream_kernel<C1, C2, C3, COMPACT>), lds_bytes);
-  const int blocks = group_grid(g.rows, lds_bytes, 3);      // 2 per CU for the head's groups (66 KB), 3 for SA3's (52 KB)
-  hipLaunchKernelGGL((mlp_group_stream_kernel<C1, C2, C3, COMPACT>), dim3(blocks), dim3(256), lds_bytes, stream, g);
-  return det6d_check_launch("det6d_mlp_group3 (streaming)");
-}
+// The widths these kernels are built for (Det6D's SA3 and head-SA groups), the waves per 32-row tile of the one-pass form (8 for
+// the head's groups: two waves per SIMD from ONE workgroup, the 99 KB of LDS allow only one workgroup per CU; 4 for the SA3
+// groups: several workgroups per CU) and the bit of DET6D_GROUP_STREAM that selects the streaming form.
+constexpr struct { int c1, c2, c3, waves, stream_bit; } kGroupTable[] = {
+    {128, 128, 256, 4, 0}, {128, 256, 256, 4, 4}, {256, 256, 512, 8, 2}, {256, 512, 1024, 8, 1}};
+constexpr int group_key(int row, int route, bool compact) { return (row * 3 + route) * 2 + compact; }      // det6d_mlp_group3's switch
 
-template <int C1, int C2, int C3, bool COMPACT, int NW>
-int launch_group(const GroupArgs &g, hipStream_t stream) {
-  const size_t lds_bytes = sizeof(float) * (32 * (size_t)(C1 + 1 + C2 + 1) + 64 + NW * 64 * kGroupVW<C3 / (32 * NW)> + 4);   // + tags + store scratch + drawn tiles
-  DET6D_MAX_DYNAMIC_LDS((mlp_group_kernel<C1, C2, C3, COMPACT, NW>), lds_bytes);
-  const int blocks = group_grid(g.rows, lds_bytes, 4);
-#ifdef DET6D_EXPERIMENTS
-  static bool phase_set = false;
-  if (!phase_set) {
-    const int pc2 = det6d_env_int("DET6D_GROUP_PHASE_C2", 512), pc3 = det6d_env_int("DET6D_GROUP_PHASE_C3", 1024);
-    hipMemcpyToSymbol(HIP_SYMBOL(d6_group_phase_c2), &pc2, sizeof(int));
-    hipMemcpyToSymbol(HIP_SYMBOL(d6_group_phase_c3), &pc3, sizeof(int));
-    phase_set = true;
-  }
-  static const int whatif = det6d_env_int("DET6D_GROUP_WHATIF", 0);
-  static bool whatif_set = false;
-  if (whatif && !whatif_set) {
-    const int zero = 0;
-    hipMemcpyToSymbol(HIP_SYMBOL(d6_group_kmul), &zero, sizeof(int));
-    whatif_set = true;
-  }
-#endif
-  hipLaunchKernelGGL((mlp_group_kernel<C1, C2, C3, COMPACT, NW>), dim3(blocks), dim3(64 * NW), lds_bytes, stream, g);
-  return det6d_check_launch("det6d_mlp_group3");
+// The plan of det6d_mlp_group3 (dense rows: b scenes x m centres x ns rows; compact: a row list of `capacity` rows): refusal,
+// or the table row (`row`), the route and its launch geometry.  b == 0 asks about the widths alone.
+static int group_plan(int c1, int c2, int c3, int ns, int b, int m, bool compact, int capacity, int &row, det6d_launch_plan &p) {
+  for (row = 0; row < 4 && (kGroupTable[row].c1 != c1 || kGroupTable[row].c2 != c2 || kGroupTable[row].c3 != c3); ++row) {}
+  if (row == 4 || b < 0 || (!compact && ns != 16 && ns != 32)) return DET6D_EINVAL;
+  if (b && (compact ? (capacity < 0 || (capacity & 127)) : (m <= 0 || (ns == 16 && (m & 1))))) return DET6D_EINVAL;   // ns = 16: two centres of one tile must share the scene
+  const long long rows = !b ? 0 : compact ? capacity : (long long)b * m * ns;
+  if ((rows & 31) || rows > 0x7fffffff) return DET6D_EINVAL;
+  // DET6D_GROUP_STREAM (bit mask, default 3): the table rows that take the streaming form.  Head's wide group (bit 1): within
+  // +-1 % of the one-pass form in the pipeline once that form fetched its first weight blocks ahead of the producing phase
+  // (12.98 vs 12.87 k scenes/s, ray-cast scenes 6.06 vs 6.09 k).  Head's narrow group (bit 2): its one-pass form holds 143
+  // registers with eight waves, i.e. one workgroup per CU; the streaming form runs it 8-10 % faster with the chip full (196 ->
+  // 180 us, ray-cast scenes 446 -> 400 us) and the pipeline gains 0.5-0.7 %.  Round 6, 80-scene passes: in the EXPERIMENTS build
+  // the wide group streaming and eight waves per tile for SA3's [128 -> 256 -> 256] looked like +4.3 % / +5.2 % / together
+  // +10.3 % (scripts/r06/gpu_t4.sh) — an artefact: that build's one-pass kernels carry phase timers.  The same A/B in the KNOBS
+  // build (scripts/r06/gpu_t6.sh, interleaved, two repeats): round-5 settings 15 034 scenes/s; wide group streaming 15 171
+  // (+0.9 %); SA3 with eight waves 14 732 (-2.0 %); SA3's wide group streaming too (mask 7) 15 114; pipelined linear slab 15 138
+  // (+0.7 %).  DET6D_GROUP_WAVES (experiments build) overrides the table's waves, DET6D_GROUP_SA3_WAVES (knobs build) SA3's.
+  static const int stream_form = det6d_env_int("DET6D_GROUP_STREAM", 3), nw_env = det6d_env_int("DET6D_GROUP_WAVES", 0),
+                   sa3_waves = det6d_env_int("DET6D_GROUP_SA3_WAVES", 4);
+  const bool stream = (stream_form & kGroupTable[row].stream_bit) != 0;
+  const int nw = !stream && c2 >= 256 && (nw_env ? nw_env : c1 == 128 ? sa3_waves : kGroupTable[row].waves) == 8 ? 8 : 4;
+  const size_t lds_bytes = stream ? group_stream_lds_bytes(c1, c3) : group_lds_bytes(c1, c2, c3, nw);
+  // persistent grid: the workgroups the chip holds at a time by their LDS (streaming: 2 per CU for the head's groups, 66 KB, 3 for SA3's, 52 KB)
+  const int per_cu = det6d_min((int)((160 * 1024) / lds_bytes), stream ? 3 : 4);
+  p = det6d_launch_plan{stream ? DET6D_GROUP_STREAM : nw == 8 ? DET6D_GROUP_ONEPASS8 : DET6D_GROUP_ONEPASS4,
+                        det6d_min((int)(rows / 32), 256 * per_cu), 1, 64 * nw, (unsigned)lds_bytes, 32};
+  return DET6D_OK;
 }
 
 }  // namespace
@@ -723,14 +726,14 @@ extern "C" __attribute__((visibility("default"))) int det6d_dbg_group_phase(unsi
 }
 #endif
 
-// widths this kernel is built for (Det6D's SA3 and head-SA groups)
-static bool group_widths_ok(int c1, int c2, int c3) {
-  return (c1 == 128 && c2 == 128 && c3 == 256) || (c1 == 128 && c2 == 256 && c3 == 256) || (c1 == 256 && c2 == 256 && c3 == 512) ||
-         (c1 == 256 && c2 == 512 && c3 == 1024);
+DET6D_API int det6d_mlp_group3_plan(int c1, int c2, int c3, int ns, int b, int m, int compact, int capacity, det6d_launch_plan *plan) {
+  int row;
+  return plan ? group_plan(c1, c2, c3, ns, b, m, compact != 0, capacity, row, *plan) : DET6D_EINVAL;
 }
 
 DET6D_API int det6d_mlp_group3_supported(int c1, int c2, int c3, int ns, int compact) {
-  return group_widths_ok(c1, c2, c3) && (compact || ns == 16 || ns == 32) ? 1 : 0;
+  det6d_launch_plan p;
+  return det6d_mlp_group3_plan(c1, c2, c3, ns, 0, 0, compact, 0, &p) == DET6D_OK ? 1 : 0;
 }
 
 DET6D_API int det6d_mlp_group3(int rows, const float *p, int ldp, int pcol0, const float *w1, int ldw1, const float *s1, int c1,
@@ -739,16 +742,15 @@ DET6D_API int det6d_mlp_group3(int rows, const float *p, int ldp, int pcol0, con
                                int ns, const int *cnt, int *hdr, const int *crow_p, const int *crow_c, float *y, int ldy,
                                int col0, det6d_stream_t stream) {
   D6_GEMM_PRIO_HOST();
-  if (rows < 0 || (rows & 31) || !p || !w1 || !w2 || !w3 || !s1 || !s2 || !s3 || !pts || !ctr || !y) return DET6D_EINVAL;
-  if (!group_widths_ok(c1, c2, c3)) return DET6D_EINVAL;
+  const bool compact = hdr != nullptr;
+  if (rows < 0 || !p || !w1 || !w2 || !w3 || !s1 || !s2 || !s3 || !pts || !ctr || !y) return DET6D_EINVAL;
   if ((ldp & 3) || (pcol0 & 3) || (ldw1 & 3) || ldp < pcol0 + c1 || ldw1 < c1 || ldw2 < c2 || ldw3 < c3 || ldpts < 3 || ldctr < 3)
     return DET6D_EINVAL;
   if (((uintptr_t)p | (uintptr_t)w1 | (uintptr_t)s1) & 15) return DET6D_EINVAL;
   if ((size_t)c1 * ldw2 * 4 >= 0xfff00000ull || (size_t)c2 * ldw3 * 4 >= 0xfff00000ull) return DET6D_EINVAL;
-  const bool compact = hdr != nullptr;
-  if (compact ? (!crow_p || !crow_c || (rows & 127)) : (!idx || !cnt || n <= 0 || m <= 0 || (ns != 16 && ns != 32) || rows % (m * ns)))
-    return DET6D_EINVAL;
-  if (!compact && ns == 16 && (m & 1)) return DET6D_EINVAL;   // two centres of one tile must share the scene
+  if (compact ? (!crow_p || !crow_c) : (!idx || !cnt || n <= 0 || m <= 0 || (ns != 16 && ns != 32) || rows % (m * ns))) return DET6D_EINVAL;
+  int row; det6d_launch_plan lp;
+  if (group_plan(c1, c2, c3, ns, compact ? 1 : rows / (m * ns), m, compact, rows, row, lp) != DET6D_OK) return DET6D_EINVAL;
   if (rows == 0) return DET6D_OK;
   GroupArgs g;
   g.rows = rows; g.p = p; g.ldp = ldp; g.pcol0 = pcol0;
@@ -764,41 +766,39 @@ DET6D_API int det6d_mlp_group3(int rows, const float *p, int ldp, int pcol0, con
   static const int pre_entries = det6d_env_int("DET6D_GROUP_PRE", 1);
   g.pre = pre_entries;
   g.yvec = (!(ldy & 3) && !(col0 & 3) && !((uintptr_t)y & 15)) ? 1 : 0;
-  hipStream_t s = (hipStream_t)stream;
-  // waves per 32-row tile: 8 for the head's groups (two waves per SIMD from ONE workgroup: the 99 KB of LDS allow only one
-  // workgroup per CU), 4 for the SA3 groups (several workgroups per CU); DET6D_GROUP_WAVES (experiments build) overrides
-  static const int nw_env = det6d_env_int("DET6D_GROUP_WAVES", 0);
-  // DET6D_GROUP_STREAM (bit mask): 1 = the streaming form (two workgroups per CU) for the head's wide group
-  // [256 -> 512 -> 1024], 2 = for its narrow group [256 -> 256 -> 512], 3 = both, 0 = the one-pass form everywhere.  Same
-  // bits.  Wide group: within +-1 % of the one-pass form in the pipeline once that form fetched its first weight blocks
-  // ahead of the producing phase (12.98 vs 12.87 k scenes/s, ray-cast scenes 6.06 vs 6.09 k).  Narrow group (default):
-  // its one-pass form holds 143 registers with eight waves, i.e. one workgroup per CU; the streaming form runs it 8-10 %
-  // faster with the chip full (196 -> 180 us, ray-cast scenes 446 -> 400 us) and the pipeline gains 0.5-0.7 %.
-  // Round 6, at the 80-scene pass size the bench runs since round 5: in the EXPERIMENTS build the streaming form of the wide
-  // group and eight waves per tile for SA3's [128 -> 256 -> 256] group looked like +4.3 % / +5.2 % / together +10.3 %
-  // (scripts/r06/gpu_t4.sh) — an artefact: that build's one-pass kernels carry phase timers.  The same A/B in the KNOBS build
-  // (the shipped kernels with the switches live, scripts/r06/gpu_t6.sh, interleaved, two repeats): round-5 settings 15 034
-  // scenes/s; wide group streaming 15 171 (+0.9 %); SA3 with eight waves 14 732 (-2.0 %); SA3's wide group streaming too (mask
-  // 7) 15 114; pipelined linear slab 15 138 (+0.7 %).  Default: mask 3, SA3 stays at four waves.
-  static const int stream_form = det6d_env_int("DET6D_GROUP_STREAM", 3);
-  if ((stream_form & 1) && c1 == 256 && c2 == 512 && c3 == 1024)
-    return compact ? launch_group_stream<256, 512, 1024, true>(g, s) : launch_group_stream<256, 512, 1024, false>(g, s);
-  if ((stream_form & 2) && c1 == 256 && c2 == 256 && c3 == 512)
-    return compact ? launch_group_stream<256, 256, 512, true>(g, s) : launch_group_stream<256, 256, 512, false>(g, s);
-  if ((stream_form & 4) && c1 == 128 && c2 == 256 && c3 == 256)      // SA3's wide group (three workgroups per CU)
-    return compact ? launch_group_stream<128, 256, 256, true>(g, s) : launch_group_stream<128, 256, 256, false>(g, s);
-#define D6_GROUP(A, B, C, NWD)                                                                        \
-  if (c1 == A && c2 == B && c3 == C) {                                                                \
-    if ((nw_env ? nw_env : NWD) == 8 && B >= 256)                                                     \
-      return compact ? launch_group<A, B, C, true, (B >= 256 ? 8 : 4)>(g, s) : launch_group<A, B, C, false, (B >= 256 ? 8 : 4)>(g, s); \
-    return compact ? launch_group<A, B, C, true, 4>(g, s) : launch_group<A, B, C, false, 4>(g, s);    \
+#ifdef DET6D_EXPERIMENTS
+  static bool phase_set = false;
+  if (lp.route != DET6D_GROUP_STREAM && !phase_set) {      // the one-pass kernels' phase timers and what-if switch
+    const int pc2 = det6d_env_int("DET6D_GROUP_PHASE_C2", 512), pc3 = det6d_env_int("DET6D_GROUP_PHASE_C3", 1024), zero = 0;
+    hipMemcpyToSymbol(HIP_SYMBOL(d6_group_phase_c2), &pc2, sizeof(int));
+    hipMemcpyToSymbol(HIP_SYMBOL(d6_group_phase_c3), &pc3, sizeof(int));
+    if (det6d_env_int("DET6D_GROUP_WHATIF", 0)) hipMemcpyToSymbol(HIP_SYMBOL(d6_group_kmul), &zero, sizeof(int));
+    phase_set = true;
   }
-  static const int sa3_waves = det6d_env_int("DET6D_GROUP_SA3_WAVES", 4);      // knobs build: 8 = eight waves per tile (slower: see below)
-  D6_GROUP(128, 128, 256, 4)
-  if (sa3_waves != 8) { D6_GROUP(128, 256, 256, 4) }
-  D6_GROUP(128, 256, 256, 8)
-  D6_GROUP(256, 256, 512, 8)
-  D6_GROUP(256, 512, 1024, 8)
-#undef D6_GROUP
-  return DET6D_EINVAL;
+#endif
+  hipStream_t s = (hipStream_t)stream;
+  const char *what = lp.route == DET6D_GROUP_STREAM ? "det6d_mlp_group3 (streaming)" : "det6d_mlp_group3";
+  switch (group_key(row, lp.route, compact)) {      // the instance of (row of kGroupTable, route, compact)
+    case group_key(0, DET6D_GROUP_ONEPASS4, false): return det6d_launch<mlp_group_kernel<128, 128, 256, false, 4>>(g, lp, s, what);
+    case group_key(0, DET6D_GROUP_ONEPASS4, true): return det6d_launch<mlp_group_kernel<128, 128, 256, true, 4>>(g, lp, s, what);
+    case group_key(1, DET6D_GROUP_STREAM, false): return det6d_launch<mlp_group_stream_kernel<128, 256, 256, false>>(g, lp, s, what);
+    case group_key(1, DET6D_GROUP_STREAM, true): return det6d_launch<mlp_group_stream_kernel<128, 256, 256, true>>(g, lp, s, what);
+    case group_key(1, DET6D_GROUP_ONEPASS4, false): return det6d_launch<mlp_group_kernel<128, 256, 256, false, 4>>(g, lp, s, what);
+    case group_key(1, DET6D_GROUP_ONEPASS4, true): return det6d_launch<mlp_group_kernel<128, 256, 256, true, 4>>(g, lp, s, what);
+    case group_key(1, DET6D_GROUP_ONEPASS8, false): return det6d_launch<mlp_group_kernel<128, 256, 256, false, 8>>(g, lp, s, what);
+    case group_key(1, DET6D_GROUP_ONEPASS8, true): return det6d_launch<mlp_group_kernel<128, 256, 256, true, 8>>(g, lp, s, what);
+    case group_key(2, DET6D_GROUP_STREAM, false): return det6d_launch<mlp_group_stream_kernel<256, 256, 512, false>>(g, lp, s, what);
+    case group_key(2, DET6D_GROUP_STREAM, true): return det6d_launch<mlp_group_stream_kernel<256, 256, 512, true>>(g, lp, s, what);
+    case group_key(2, DET6D_GROUP_ONEPASS4, false): return det6d_launch<mlp_group_kernel<256, 256, 512, false, 4>>(g, lp, s, what);
+    case group_key(2, DET6D_GROUP_ONEPASS4, true): return det6d_launch<mlp_group_kernel<256, 256, 512, true, 4>>(g, lp, s, what);
+    case group_key(2, DET6D_GROUP_ONEPASS8, false): return det6d_launch<mlp_group_kernel<256, 256, 512, false, 8>>(g, lp, s, what);
+    case group_key(2, DET6D_GROUP_ONEPASS8, true): return det6d_launch<mlp_group_kernel<256, 256, 512, true, 8>>(g, lp, s, what);
+    case group_key(3, DET6D_GROUP_STREAM, false): return det6d_launch<mlp_group_stream_kernel<256, 512, 1024, false>>(g, lp, s, what);
+    case group_key(3, DET6D_GROUP_STREAM, true): return det6d_launch<mlp_group_stream_kernel<256, 512, 1024, true>>(g, lp, s, what);
+    case group_key(3, DET6D_GROUP_ONEPASS4, false): return det6d_launch<mlp_group_kernel<256, 512, 1024, false, 4>>(g, lp, s, what);
+    case group_key(3, DET6D_GROUP_ONEPASS4, true): return det6d_launch<mlp_group_kernel<256, 512, 1024, true, 4>>(g, lp, s, what);
+    case group_key(3, DET6D_GROUP_ONEPASS8, false): return det6d_launch<mlp_group_kernel<256, 512, 1024, false, 8>>(g, lp, s, what);
+    case group_key(3, DET6D_GROUP_ONEPASS8, true): return det6d_launch<mlp_group_kernel<256, 512, 1024, true, 8>>(g, lp, s, what);
+    default: return DET6D_EINVAL;      // unreachable: group_plan names no other (row, route)
+  }
 }

@@ -585,11 +585,16 @@ __global__ __launch_bounds__(256, 2) void mlp_rows_wave_kernel(const RowsArgs g)
 
 }  // namespace
 
-// Validates a stack description and derives the LDS plan: k0 (input width), wa / wb (row widths of the two activation
-// buffers), kchunk (columns of the input held in LDS at a time).  Shared by det6d_mlp_rows and det6d_mlp_rows_supported.
-static int rows_plan(int nchains, const int *nlayers, const det6d_rows_layer *layers, RowsArgs &g) {
-  if (nchains < 1 || nchains > 2 || !nlayers || !layers) return DET6D_EINVAL;
-  int wa = 0, wb = 0, k0 = -1, off = 0;
+// The plan of det6d_mlp_rows: validates a stack description over `rows` rows of x (rows, ldx) from column xcol0, derives the
+// LDS layout (k0 = input width, wa / wb = row widths of the two activation buffers, kchunk = columns of the input held in LDS
+// at a time) into `g` and chooses the route and its launch geometry into `p`.  Shape facts only: of x it takes whether its
+// address is 16-byte aligned.  Shared by det6d_mlp_rows, det6d_mlp_rows_plan and det6d_mlp_rows_supported.
+static int rows_plan(int rows, int ldx, int xcol0, bool x_aligned16, int nchains, const int *nlayers, const det6d_rows_layer *layers,
+                     RowsArgs &g, det6d_launch_plan &p) {
+  if (rows < 0 || ldx <= 0 || xcol0 < 0 || nchains < 1 || nchains > 2 || !nlayers || !layers) return DET6D_EINVAL;
+  int wa = 0, wb = 0, k0 = -1, off = 0, max_tiles = 0;
+  // (32-bit byte offsets into the input and every output: the buffer-store epilogues and the wave-private kernel)
+  bool fits32 = (size_t)rows * ldx * 4 < 0xfff00000ull;
   for (int c = 0; c < 2; ++c) g.nlayers[c] = 0;
   for (int c = 0; c < nchains; ++c) {
     const int nl = nlayers[c];
@@ -610,11 +615,15 @@ static int rows_plan(int nchains, const int *nlayers, const det6d_rows_layer *la
       if (L.out && (L.ldo < L.ocol0 + L.n)) return DET6D_EINVAL;
       if ((size_t)L.k * L.ldw * 4 >= 0xfff00000ull) return DET6D_EINVAL;
       if (l & 1) { if (L.k > wb) wb = L.k; } else { if (L.k > wa) wa = L.k; }     // layer l reads XA (even l) / XB (odd l)
+      fits32 = fits32 && (!L.out || (size_t)rows * L.ldo * 4 < 0xfff00000ull);
+      if ((L.n + 31) / 32 > max_tiles) max_tiles = (L.n + 31) / 32;
       kin = L.n;
       g.layers[c][l] = L;
     }
     off += nl;
   }
+  if (xcol0 + k0 > ldx) return DET6D_EINVAL;
+  g.rows = rows; g.ldx = ldx; g.xcol0 = xcol0;
   g.k0 = k0; g.wa = wa; g.wb = wb > 0 ? wb : 1;
   g.kchunk = k0;
   if (k0 >= 512 && (k0 % 256) == 0) {      // a wide input whose first layers have at most four column tiles: K-chunks of 256
@@ -627,78 +636,35 @@ static int rows_plan(int nchains, const int *nlayers, const det6d_rows_layer *la
     }
     if (narrow) { g.kchunk = 256; g.wa = wa_rest; }
   }
-  // one 32-row tile's two activation buffers must fit the CU's 160 KB (64-row tiles are chosen only for narrow stacks)
-  if (sizeof(float) * 32 * ((size_t)(g.wa + 1) + (size_t)(g.wb + 1)) > 160 * 1024) return DET6D_EINVAL;
-  return DET6D_OK;
-}
-
-// 1 when det6d_mlp_rows accepts this stack (widths, chain structure, LDS), else 0: the host asks BEFORE it routes a stack of
-// plain layers here instead of through one det6d_linear per layer (e.g. a [1024 -> 1024 -> ..] tower does not fit).
-DET6D_API int det6d_mlp_rows_supported(int nchains, const int *nlayers, const det6d_rows_layer *layers) {
-  RowsArgs g;
-  return rows_plan(nchains, nlayers, layers, g) == DET6D_OK ? 1 : 0;
-}
-
-DET6D_API int det6d_mlp_rows(int rows, const float *x, int ldx, int xcol0, int nchains, const int *nlayers,
-                             const det6d_rows_layer *layers, det6d_stream_t stream) {
-  D6_GEMM_PRIO_HOST();
-  if (rows < 0 || (!x && rows > 0) || ldx <= 0 || xcol0 < 0) return DET6D_EINVAL;     // (no rows: an empty tensor has no address)
-  RowsArgs g;
-  if (rows_plan(nchains, nlayers, layers, g) != DET6D_OK) return DET6D_EINVAL;
-  g.rows = rows; g.x = x; g.ldx = ldx; g.xcol0 = xcol0;
-  const int k0 = g.k0;
-  if (xcol0 + k0 > ldx) return DET6D_EINVAL;
-  g.vec4 = ((k0 & 3) == 0 && (ldx & 3) == 0 && (xcol0 & 3) == 0 && (((uintptr_t)x) & 15) == 0) ? 1 : 0;
-  if (rows == 0) return DET6D_OK;
-  // the first level's stack ([96 -> 64 -> 32 -> 1] over 4096 centres per scene): weights resident in registers
-  static const int resident_env = det6d_env_int("DET6D_ROWS_RESIDENT", 2);
-  // DET6D_ROWS_RESIDENT (knobs build): 2 (default) = wave-private tiles (round 6), 1 = the four-wave resident kernel of round 5,
-  // 0 = the general kernel
-  // (32-bit byte offsets into the input and every output: the buffer-store epilogues and the wave-private kernel)
-  bool fits32 = (size_t)rows * ldx * 4 < 0xfff00000ull;
-  {
-    int nl_all = 0;
-    for (int c = 0; c < nchains; ++c) nl_all += nlayers[c];
-    for (int l = 0; l < nl_all; ++l) fits32 = fits32 && (!layers[l].out || (size_t)rows * layers[l].ldo * 4 < 0xfff00000ull);
-  }
+  g.vec4 = ((k0 & 3) == 0 && (ldx & 3) == 0 && (xcol0 & 3) == 0 && x_aligned16) ? 1 : 0;
   g.fits32 = fits32 ? 1 : 0;
-  // (the wave-private kernel forms its scalar byte offsets in signed 32-bit arithmetic: half the range)
-  const bool fits31 = fits32 && (size_t)rows * ldx * 4 < 0x7ff00000ull;
-  // the SA1 shape [96 -> 64 -> 32 -> n <= 32] over many rows, whole input in LDS
+  // the two activation buffers of a tile of rb 32-row blocks: a 32-row tile's must fit the CU's 160 KB
+  const auto tile_lds = [&](int rb) { return sizeof(float) * 32 * rb * ((size_t)(g.wa + 1) + (size_t)(g.wb + 1)); };
+  if (tile_lds(1) > 160 * 1024) return DET6D_EINVAL;
+  // the first level's stack ([96 -> 64 -> 32 -> n <= 32] over 4096 centres per scene, whole input in LDS): weights resident in
+  // registers.  DET6D_ROWS_RESIDENT (knobs build): 2 (default) = wave-private tiles (round 6), 1 = the four-wave resident
+  // kernel of round 5, 0 = the general kernel
+  static const int resident_env = det6d_env_int("DET6D_ROWS_RESIDENT", 2);
   const bool sa1 = nchains == 1 && nlayers[0] == 3 && g.kchunk == g.k0 && g.vec4 && rows >= 16384 && layers[0].k == 96 &&
                    layers[0].n == 64 && layers[1].n == 32 && layers[2].n <= 32 && layers[0].ldw >= 64 && layers[1].ldw >= 32;
+  // (the wave-private kernel forms its scalar byte offsets in signed 32-bit arithmetic: half the range)
+  const bool fits31 = fits32 && (size_t)rows * ldx * 4 < 0x7ff00000ull;
   if (sa1 && resident_env == 2 && (rows & 31) == 0 && fits31) {
-    constexpr size_t lds_wave = sizeof(float) * ((64 + 32) * 32 + 4 * 32 * 97);
-    DET6D_MAX_DYNAMIC_LDS((mlp_rows_wave_kernel<96, 64, 32>), lds_wave);
-    int blocks = ((rows + 31) / 32 + 3) / 4;
-    if (blocks > 512) blocks = 512;                  // two workgroups of four independent waves per CU, persistent over the tiles
-    hipLaunchKernelGGL((mlp_rows_wave_kernel<96, 64, 32>), dim3(blocks), dim3(256), lds_wave, (hipStream_t)stream, g);
-    return det6d_check_launch("det6d_mlp_rows");
+    // two workgroups of four independent waves per CU, persistent over the tiles
+    p = det6d_launch_plan{DET6D_ROWS_W, det6d_min(det6d_divup(rows, 128), 512), 1, 256, sizeof(float) * ((64 + 32) * 32 + 4 * 32 * 97), 32};
+    return DET6D_OK;
   }
   if (sa1 && resident_env) {
-    constexpr size_t lds_resident = sizeof(float) * (2 * 64 * 97 + 64 * 65);
-    DET6D_MAX_DYNAMIC_LDS((mlp_rows_resident_kernel<96, 64, 32>), lds_resident);
-    int blocks = (rows + 63) / 64;
-    if (blocks > 512) blocks = 512;                  // two workgroups per CU (66 KB of LDS each), persistent over the tiles
-    hipLaunchKernelGGL((mlp_rows_resident_kernel<96, 64, 32>), dim3(blocks), dim3(256), lds_resident, (hipStream_t)stream, g);
-    return det6d_check_launch("det6d_mlp_rows");
+    // two workgroups per CU (66 KB of LDS each), persistent over the tiles
+    p = det6d_launch_plan{DET6D_ROWS_R, det6d_min(det6d_divup(rows, 64), 512), 1, 256, sizeof(float) * (2 * 64 * 97 + 64 * 65), 64};
+    return DET6D_OK;
   }
-  // narrow stacks (every layer at most two column tiles, single chain, many rows): 64-row tiles
-  int max_tiles = 0;
-  for (int c = 0, o = 0; c < nchains; o += nlayers[c], ++c)
-    for (int l = 0; l < nlayers[c]; ++l) max_tiles = max_tiles > (layers[o + l].n + 31) / 32 ? max_tiles : (layers[o + l].n + 31) / 32;
-  // DET6D_ROWS_RB: 2 (default) = 64-row tiles for narrow stacks over >= 16384 rows, 3 = over any number of rows, 1 = never
+  // narrow stacks (every layer at most two column tiles, whole input in LDS, many rows): 64-row tiles where they fit (those
+  // of a narrow stack with a long input, e.g. [640 -> 64 -> 3], do not).  DET6D_ROWS_RB: 2 (default) = over >= 16384 rows,
+  // 3 = over any number of rows, 1 = never
   static const int rb_env = det6d_env_int("DET6D_ROWS_RB", 2);
-  // (a 64-row tile of a narrow stack with a long input, e.g. [640 -> 64 -> 3], does not fit the CU: rows_plan promised 32-row tiles)
-  const bool fits64 = sizeof(float) * 64 * ((size_t)(g.wa + 1) + (size_t)(g.wb + 1)) <= 160 * 1024;
-  const int rb = (rb_env >= 2 && g.kchunk == g.k0 && max_tiles <= 2 && fits64 && (rows >= 16384 || rb_env == 3)) ? 2 : 1;
-  const size_t lds_bytes = sizeof(float) * 32 * rb * ((size_t)(g.wa + 1) + (size_t)(g.wb + 1));
-  if (lds_bytes > 160 * 1024) return DET6D_EINVAL;
-  // (the need varies per call: the limit is set once per device, to the CU's 160 KB)
-  DET6D_MAX_DYNAMIC_LDS((mlp_rows_kernel<false, 1>), 160 * 1024);
-  DET6D_MAX_DYNAMIC_LDS((mlp_rows_kernel<true, 1>), 160 * 1024);
-  DET6D_MAX_DYNAMIC_LDS((mlp_rows_kernel<false, 2>), 160 * 1024);
-  int blocks = (rows + 32 * rb - 1) / (32 * rb);
+  const int rb = (rb_env >= 2 && g.kchunk == g.k0 && max_tiles <= 2 && tile_lds(2) <= 160 * 1024 && (rows >= 16384 || rb_env == 3)) ? 2 : 1;
+  const size_t lds_bytes = tile_lds(rb);
   // persistent walk over the tiles by as many workgroups as the chip HOLDS at a time (LDS: 3 per CU for the SA stacks; 128
   // registers: at most 4): a grid of 1024 on 768 slots ran its last 256 workgroups on a third of the chip (80-scene passes,
   // SA1's stack: 768: 132 us, 1024: 153, 1536: 134, 2048: 139, 512: 161; scripts/r05/gpu_t29.sh).  DET6D_ROWS_BLOCKS:
@@ -707,12 +673,43 @@ DET6D_API int det6d_mlp_rows(int rows, const float *x, int ldx, int xcol0, int n
   per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
   static const int blocks_env = det6d_env_int("DET6D_ROWS_BLOCKS", 0);
   const int blocks_cap = blocks_env > 0 ? blocks_env : 256 * per_cu / nchains;     // the grid is (blocks, chains)
-  if (blocks > blocks_cap) blocks = blocks_cap;
-  if (g.kchunk < g.k0)
-    hipLaunchKernelGGL((mlp_rows_kernel<true, 1>), dim3(blocks, nchains), dim3(256), lds_bytes, (hipStream_t)stream, g);
-  else if (rb == 2)
-    hipLaunchKernelGGL((mlp_rows_kernel<false, 2>), dim3(blocks, nchains), dim3(256), lds_bytes, (hipStream_t)stream, g);
-  else
-    hipLaunchKernelGGL((mlp_rows_kernel<false, 1>), dim3(blocks, nchains), dim3(256), lds_bytes, (hipStream_t)stream, g);
-  return det6d_check_launch("det6d_mlp_rows");
+  p = det6d_launch_plan{g.kchunk < g.k0 ? DET6D_ROWS_GC : rb == 2 ? DET6D_ROWS_G2 : DET6D_ROWS_G1,
+                        det6d_min(det6d_divup(rows, 32 * rb), blocks_cap), nchains, 256, (unsigned)lds_bytes, 32 * rb};
+  return DET6D_OK;
+}
+
+DET6D_API int det6d_mlp_rows_plan(int rows, int ldx, int xcol0, int x_aligned16, int nchains, const int *nlayers,
+                                  const det6d_rows_layer *layers, det6d_launch_plan *plan) {
+  RowsArgs g;
+  return plan ? rows_plan(rows, ldx, xcol0, x_aligned16 != 0, nchains, nlayers, layers, g, *plan) : DET6D_EINVAL;
+}
+
+// 1 when det6d_mlp_rows accepts this stack (widths, chain structure, LDS) over an input as wide as the stack reads, else 0:
+// the host asks BEFORE it routes a stack of plain layers here instead of through one det6d_linear per layer (e.g. a
+// [1024 -> 1024 -> ..] tower does not fit).
+DET6D_API int det6d_mlp_rows_supported(int nchains, const int *nlayers, const det6d_rows_layer *layers) {
+  det6d_launch_plan p;
+  return det6d_mlp_rows_plan(0, layers ? layers[0].k : 0, 0, 0, nchains, nlayers, layers, &p) == DET6D_OK ? 1 : 0;
+}
+
+DET6D_API int det6d_mlp_rows(int rows, const float *x, int ldx, int xcol0, int nchains, const int *nlayers,
+                             const det6d_rows_layer *layers, det6d_stream_t stream) {
+  D6_GEMM_PRIO_HOST();
+  if (!x && rows > 0) return DET6D_EINVAL;     // (no rows: an empty tensor has no address)
+  RowsArgs g;
+  det6d_launch_plan p;
+  if (rows_plan(rows, ldx, xcol0, (((uintptr_t)x) & 15) == 0, nchains, nlayers, layers, g, p) != DET6D_OK) return DET6D_EINVAL;
+  if (rows == 0) return DET6D_OK;
+  g.x = x;
+  hipStream_t s = (hipStream_t)stream;
+  const char *what = "det6d_mlp_rows";
+  switch (p.route) {
+    case DET6D_ROWS_W: return det6d_launch<mlp_rows_wave_kernel<96, 64, 32>>(g, p, s, what);
+    case DET6D_ROWS_R: return det6d_launch<mlp_rows_resident_kernel<96, 64, 32>>(g, p, s, what);
+    // (the general kernels' need varies per call: the limit is set once per device, to the CU's 160 KB)
+    case DET6D_ROWS_G1: return det6d_launch<mlp_rows_kernel<false, 1>>(g, p, s, what, 160 * 1024);
+    case DET6D_ROWS_GC: return det6d_launch<mlp_rows_kernel<true, 1>>(g, p, s, what, 160 * 1024);
+    case DET6D_ROWS_G2: return det6d_launch<mlp_rows_kernel<false, 2>>(g, p, s, what, 160 * 1024);
+    default: return DET6D_EINVAL;      // unreachable: rows_plan names no other route
+  }
 }

@@ -287,10 +287,13 @@ def group_expand(p, pcol0, w, shift, act, c1, rows_pts, ctr, out, idx=None, comp
 GROUP_KERNEL = L.experiment_switch('DET6D_NO_GROUP_KERNEL') is None
 
 
-def group_kernel_eligible(layers, ns, compact):
+def group_kernel_eligible(layers, ns, compact, b=0, m=0):
+    """can a grouped 3-layer MLP run as ONE det6d_mlp_group3 launch?  The library decides (det6d_mlp_group3_plan, the
+    function the launch itself routes by); b = 0: by its widths alone (compact lists: b, m are not looked at)"""
     if not GROUP_KERNEL or len(layers) != 3 or not all(l[3] == 1 for l in layers):
         return False
-    return bool(L.lib().det6d_mlp_group3_supported(layers[0][2], layers[1][2], layers[2][2], ns, 1 if compact else 0))
+    return L.lib().det6d_mlp_group3_plan(layers[0][2], layers[1][2], layers[2][2], ns, b, m, 1 if compact else 0, 0,
+                                         L.LaunchPlan()) == 0
 
 
 def mlp_group3(p, pcol0, layers, rows_pts, ctr, out, col0, idx=None, cnt=None, compact=None):
@@ -510,31 +513,27 @@ def ball_query_pair_lists(xyz, new_xyz, shell_a, shell_b):
     return cnt_a, idx_a, cnt_b, idx_b, la, lb
 
 
-#: route [68 -> 64 -> 64|96 -> 128] groups through the wide register chain kernel
-CHAIN_WIDE = L.experiment_switch('DET6D_CHAIN_NO_WIDE') is None   # the C entry honours the same switch
-
-
-def chain_eligible(lda, layers, ns):
-    """can a grouped 3-layer MLP run as ONE det6d_mlp_chain3 launch?  layers: [(W, shift, cout, act)] x 3"""
-    if len(layers) != 3 or ns not in (16, 32) or not all(l[3] == 1 for l in layers):
-        return False
-    c1, c2, c3 = layers[0][2], layers[1][2], layers[2][2]
-    if lda == 68 and c1 == 64 and c2 in (64, 96) and c3 == 128:      # wide register chain (SA2-sized groups)
-        return CHAIN_WIDE
-    return lda <= 8 and c1 <= 32 and c2 <= 32 and c3 <= 64
-
-
+#: DET6D_CHAIN_NO_WIDE=1: no group through the wide register chain kernel.  The plan function of csrc/mlp_chain.hip reads the
+#: same variable (in the same builds), so the refusal below only spares the call.
+CHAIN_WIDE = L.experiment_switch('DET6D_CHAIN_NO_WIDE') is None
 #: compact-row groups through the register chain kernels (DET6D_COMPACT_NO_CHAIN=1: three det6d_linear launches)
 COMPACT_CHAIN = L.experiment_switch('DET6D_COMPACT_NO_CHAIN') is None
 
 
-def chain_compact_eligible(lda, layers):
-    if not COMPACT_CHAIN or len(layers) != 3 or not all(l[3] == 1 for l in layers):
+def chain_eligible(lda, layers, ns, b=0, m=0, compact=False):
+    """can a grouped 3-layer MLP run as ONE det6d_mlp_chain3 launch?  layers: [(W, shift, cout, act)] x 3.  The library decides
+    (det6d_mlp_chain3_plan, the function the launch itself routes by); b = 0: by its widths alone"""
+    if len(layers) != 3 or not all(l[3] == 1 for l in layers):
         return False
-    c = (layers[0][2], layers[1][2], layers[2][2])
-    if lda == 68 and c[0] == 64 and c[1] in (64, 96) and c[2] == 128:
-        return CHAIN_WIDE
-    return lda == 4 and c in ((16, 16, 32), (32, 32, 64))
+    plan = L.LaunchPlan()
+    if L.lib().det6d_mlp_chain3_plan(lda, layers[0][2], layers[1][2], layers[2][2], ns, b, m, 1 if compact else 0, 0, plan) != 0:
+        return False
+    return CHAIN_WIDE or L.CHAIN_ROUTES[plan.route] != "WIDE"
+
+
+def chain_compact_eligible(lda, layers):
+    """chain_eligible for det6d_mlp_chain3_compact (a compact row list: no nsample, no pairing of centres)"""
+    return COMPACT_CHAIN and chain_eligible(lda, layers, 0, compact=True)
 
 
 def mlp_chain3_compact(rows_pts, cr, ctr, layers, out, col0):

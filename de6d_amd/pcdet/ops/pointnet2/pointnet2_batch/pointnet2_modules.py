@@ -338,14 +338,17 @@ class _PointnetSAModuleFSBase(nn.Module):
                     x = tgt
                 col += layers[-1][2]
                 continue
-            if fused.chain_eligible(rows.shape[-1], layers, nsample):   # narrow group: one fused launch
+            if fused.chain_eligible(rows.shape[-1], layers, nsample, b, m):   # narrow group: one fused launch
                 fused.mlp_chain3(rows, idx, new_xyz, idx_cnt, layers, pooled, col)
                 col += layers[-1][2]
                 continue
-            if gi in f['expand'] and fused.group_kernel_eligible(layers, nsample, False) and (nsample == 32 or m % 2 == 0):
+            if gi in f['expand'] and fused.group_kernel_eligible(layers, nsample, False, b, m):
                 fused.mlp_group3(p_all, f['pcols'][gi], layers, rows, new_xyz, pooled, col, idx=idx, cnt=idx_cnt)
                 col += layers[-1][2]
                 continue
+            # one launch per layer.  Also the route of a group that _prepare counted as chained (by its widths) and that the
+            # library refuses at this (b, m) — odd m with nsample 16, b * m * nsample off the 32-row tiles: such a group is
+            # not in f['expand'], so its first layer is the gathered det6d_linear below
             x = None
             for li, (w, shift, cout, act) in enumerate(layers):
                 last = li == len(layers) - 1

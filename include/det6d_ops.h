@@ -308,6 +308,35 @@ int det6d_fps_fused(int b, int n_total, int lo, int hi, int m, const float *xyz,
                     float gamma, float *temp, long long temp_bytes, int *idx, int idx_stride, int idx_offset,
                     int idx_bias, det6d_stream_t stream);   /* idx_bias: added to every written index on top of lo */
 
+/* Launch plans of the fused MLP entry points (det6d_mlp_rows, det6d_mlp_chain3(_compact), det6d_mlp_group3): which kernel
+ * ("route") runs a shape and with which launch geometry, or that the entry refuses the shape.  A det6d_*_plan query and its
+ * launch entry call the SAME host function, so the entry returns DET6D_EINVAL for a shape exactly when the query does (given
+ * the entry's pointer preconditions, below) and launches what the plan says.  The queries are host arithmetic: they touch no
+ * device and need none.  They return DET6D_OK and fill *plan, or DET6D_EINVAL.
+ *   route: one of the entry's enum below; grid_x, grid_y, block: the launch; lds_bytes: its dynamic LDS; tile_rows: rows a
+ *   workgroup (route W: a wave) takes at a time.
+ * Preconditions the queries take as given and the launch entries check (DET6D_EINVAL): non-NULL pointers, leading dimensions
+ * that hold their widths, and for det6d_mlp_chain3 / _group3 the 16-byte alignment of the row (a / p), weight and shift
+ * pointers (leading dimensions of the weights multiples of 4) — tensors of a caching allocator always are. */
+typedef struct { int route; int grid_x, grid_y; int block; unsigned lds_bytes; int tile_rows; } det6d_launch_plan;
+enum {                      /* det6d_mlp_rows (csrc/mlp_rows.hip) */
+  DET6D_ROWS_W = 0,         /* [96 -> 64 -> 32 -> n <= 32], >= 16384 rows, a multiple of 32: wave-private 32-row tiles */
+  DET6D_ROWS_R = 1,         /* the same stack, any row count >= 16384: weights resident in registers, 64-row tiles */
+  DET6D_ROWS_G1 = 2,        /* general stacks, 32-row tiles */
+  DET6D_ROWS_GC = 3,        /* a wide input (k0 >= 512, k0 % 256 == 0, first layers <= 128 wide) in K-chunks of 256 */
+  DET6D_ROWS_G2 = 4         /* every layer at most two column tiles, >= 16384 rows: 64-row tiles where they fit the LDS */
+};
+enum {                      /* det6d_mlp_chain3 and det6d_mlp_chain3_compact (csrc/mlp_chain.hip) */
+  DET6D_CHAIN_WIDE = 0,     /* lda = 68, (64, 64 | 96, 128): 512-thread workgroups, weights in LDS */
+  DET6D_CHAIN_REG = 1,      /* lda = 4, (16, 16, 32) | (32, 32, 64): the register kernels */
+  DET6D_CHAIN_LDS = 2       /* dense rows only: any lda in {4, 8}, c1, c2 <= 32, c3 <= 64 */
+};
+enum {                      /* det6d_mlp_group3 (csrc/mlp_group.hip) */
+  DET6D_GROUP_STREAM = 0,   /* second layer in chunks of 128 columns streamed into the third */
+  DET6D_GROUP_ONEPASS4 = 1, /* whole layers, four waves per 32-row tile */
+  DET6D_GROUP_ONEPASS8 = 2  /* whole layers, eight waves per tile */
+};
+
 /* Short stacks of plain pointwise layers over few rows in ONE launch (csrc/mlp_rows.hip): the aggregation + confidence
  * chain of an SA layer (pointnet2_modules.py:580-607), the vote FC and the cls / reg towers of the head
  * (point_head_box6d_vote.py:33-45,157-169).  Input: columns [xcol0, xcol0 + k) of x (rows, ldx), k = layers[0].k.
@@ -323,8 +352,12 @@ typedef struct det6d_rows_layer {
 } det6d_rows_layer;
 int det6d_mlp_rows(int rows, const float *x, int ldx, int xcol0, int nchains, const int *nlayers,
                    const det6d_rows_layer *layers, det6d_stream_t stream);
-/* 1 when det6d_mlp_rows accepts this stack (same checks, incl. the 160 KB of LDS a 32-row tile's two activation buffers
- * may take), else 0 — asked by the host before it routes a stack here instead of through one det6d_linear per layer. */
+/* The plan of det6d_mlp_rows for this stack over `rows` rows of x (x_aligned16: the address of x is a multiple of 16), incl.
+ * the 160 KB of LDS a 32-row tile's two activation buffers may take.  det6d_mlp_rows_supported: 1 when the plan accepts the
+ * stack over an input exactly as wide as it reads, else 0 — asked by the host before it routes a stack here instead of
+ * through one det6d_linear per layer. */
+int det6d_mlp_rows_plan(int rows, int ldx, int xcol0, int x_aligned16, int nchains, const int *nlayers,
+                        const det6d_rows_layer *layers, det6d_launch_plan *plan);
 int det6d_mlp_rows_supported(int nchains, const int *nlayers, const det6d_rows_layer *layers);
 
 /* A wide three-layer grouped MLP in ONE launch (csrc/mlp_group.hip): layer 1 from the per-point partial sums exactly as
@@ -332,9 +365,11 @@ int det6d_mlp_rows_supported(int nchains, const int *nlayers, const det6d_rows_l
  * from L2 into the MFMA B fragments), then the max-pool: over the nsample rows of a centre with the empty-ball mask
  * (dense rows: idx (B,m,ns), cnt (B*m), ns in {16, 32}) or by class over a compact row list (hdr / crow_p / crow_c; the
  * slice of y must be zeroed: parts of one centre are combined by an integer atomic max).  Bit for bit the sequence
- * det6d_group_expand -> det6d_linear -> det6d_linear(pool).  Widths (c1, c2, c3) in {(128,128,256), (128,256,256),
- * (256,256,512), (256,512,1024)}: det6d_mlp_group3_supported says so.  Replaces the three Conv2d/BN/ReLU + mask +
- * max_pool2d of a radius group (pointnet2_modules.py:462-472) and their two intermediates in memory. */
+ * det6d_group_expand -> det6d_linear -> det6d_linear(pool).  Replaces the three Conv2d/BN/ReLU + mask + max_pool2d of a
+ * radius group (pointnet2_modules.py:462-472) and their two intermediates in memory.
+ * Which widths and row counts it accepts: det6d_mlp_group3_plan (dense rows: b scenes x m centres x ns rows; compact != 0: a
+ * list of `capacity` rows; b = 0: the widths alone, grid left 0).  det6d_mlp_group3_supported: that widths-only answer. */
+int det6d_mlp_group3_plan(int c1, int c2, int c3, int ns, int b, int m, int compact, int capacity, det6d_launch_plan *plan);
 int det6d_mlp_group3_supported(int c1, int c2, int c3, int ns, int compact);
 int det6d_mlp_group3(int rows, const float *p, int ldp, int pcol0, const float *w1, int ldw1, const float *s1, int c1,
                      const float *w2, int ldw2, const float *s2, int c2, const float *w3, int ldw3, const float *s3,
@@ -471,19 +506,19 @@ int det6d_compact_groups_pair_counted(int b, int n, int m, int smin, int split, 
 
 /* The three pointwise layers of a grouped MLP in one launch, nsample 16 or 32: identical, bit for bit, to
  *   det6d_linear(GROUPED, W1, ReLU) -> det6d_linear(ROWS, W2, ReLU) -> det6d_linear(ROWS, W3, ReLU, pool = ns, cnt)
- * but the (rows x c1), (rows x c2) intermediates never leave the CU (csrc/mlp_chain.hip).  Supported shapes:
- *   narrow: row width lda <= 8, c1, c2 <= 32, c3 <= 64 (register kernel for lda = 4 with (16,16,32) / (32,32,64),
- *           LDS kernel otherwise);
- *   wide:   lda = 68, c1 = 64, c2 = 64 or 96, c3 = 128, 16-byte aligned weights / shifts, m even when ns = 16.
- * Anything else returns DET6D_EINVAL (callers fall back to three det6d_linear calls).
+ * but the (rows x c1), (rows x c2) intermediates never leave the CU (csrc/mlp_chain.hip).  Which shapes it accepts:
+ * det6d_mlp_chain3_plan (dense rows: b scenes x m centres x ns rows; compact != 0: det6d_mlp_chain3_compact over a list of
+ * `capacity` rows; b = 0: the widths alone, grid left 0).  Anything else returns DET6D_EINVAL (callers ask first and fall
+ * back to three det6d_linear calls).
  * y[(r / ns) * ldy + col0 + c], r over b*m*ns rows. */
+int det6d_mlp_chain3_plan(int lda, int c1, int c2, int c3, int ns, int b, int m, int compact, int capacity,
+                          det6d_launch_plan *plan);
 int det6d_mlp_chain3(int rows, int n, int m, int ns, const float *a, int lda, const int *idx,
                      const float *ctr, int ldctr, const int *cnt, const float *w1, int ldw1, const float *s1,
                      int c1, const float *w2, int ldw2, const float *s2, int c2, const float *w3, int ldw3,
                      const float *s3, int c3, float *y, int ldy, int col0, det6d_stream_t stream);
 
-/* det6d_mlp_chain3 over a compact row list (register kernels only: lda = 4 with (16,16,32) / (32,32,64), or the
- * wide shapes); y[centre * ldy + col0 + c] for every centre of the list. */
+/* det6d_mlp_chain3 over a compact row list; y[centre * ldy + col0 + c] for every centre of the list. */
 int det6d_mlp_chain3_compact(int capacity, const int *hdr, const int *crow_p, const int *crow_c, const float *a,
                              int lda, const float *ctr, int ldctr, const float *w1, int ldw1, const float *s1, int c1,
                              const float *w2, int ldw2, const float *s2, int c2, const float *w3, int ldw3,

@@ -303,6 +303,211 @@ def L_supported(fused, chains):
     return bool(fused.L.lib().det6d_mlp_rows_supported(len(chains), counts, arr))
 
 
+# ---- launch plans (include/det6d_ops.h: det6d_*_plan): the host function each fused MLP entry point routes by, asked without a GPU ----
+KB160 = 160 * 1024
+CHAIN_SETS = {'wide64': (68, 64, 64, 128), 'wide96': (68, 64, 96, 128), 'reg16': (4, 16, 16, 32), 'reg32': (4, 32, 32, 64),
+              'lds': (8, 24, 32, 40)}
+GROUP_SETS = [(128, 128, 256), (128, 256, 256), (256, 256, 512), (256, 512, 1024)]
+
+
+def rows_stack(k0, *widths):
+    """[(k, n)] of a chain [k0 -> widths...]"""
+    return list(zip((k0,) + widths[:-1], widths))
+
+
+def rows_plan(rows, chains, ldx=None, xcol0=0, aligned=1):
+    """det6d_mlp_rows_plan over chains of (k, n) layers (ReLU on hidden layers, only the last one stored, ldw = n, ldo = n; the
+    query reads no memory: the pointers only have to be non-NULL) -> (accepted, plan with .name = the route's name)"""
+    from de6d_amd import _lib as L
+    flat = [(k, n, i == len(c) - 1) for c in chains for i, (k, n) in enumerate(c)]
+    arr = (L.RowsLayer * len(flat))()
+    for d, (k, n, last) in zip(arr, flat):
+        d.w, d.ldw, d.k, d.n, d.act = 0x1000, n, k, n, int(not last)
+        if last:
+            d.out, d.ldo = 0x1000, n
+    counts = (L.c_int * len(chains))(*[len(c) for c in chains])
+    plan = L.LaunchPlan()
+    rc = L.lib().det6d_mlp_rows_plan(rows, chains[0][0][0] if ldx is None else ldx, xcol0, aligned, len(chains), counts, arr, plan)
+    assert rc in (0, -1)
+    plan.name = L.ROWS_ROUTES[plan.route] if rc == 0 else None
+    if ldx is None:     # over an input as wide as the stack reads no refusal depends on the rows: the _supported query's answer
+        assert bool(L.lib().det6d_mlp_rows_supported(len(chains), counts, arr)) == (rc == 0)
+    return rc == 0, plan
+
+
+def chain_plan(lda, c1, c2, c3, ns, b, m, compact=0, capacity=0):
+    from de6d_amd import _lib as L
+    plan = L.LaunchPlan()
+    rc = L.lib().det6d_mlp_chain3_plan(lda, c1, c2, c3, ns, b, m, compact, capacity, plan)
+    assert rc in (0, -1)
+    plan.name = L.CHAIN_ROUTES[plan.route] if rc == 0 else None
+    return rc == 0, plan
+
+
+def group_plan(c1, c2, c3, ns, b, m, compact=0, capacity=0):
+    from de6d_amd import _lib as L
+    plan = L.LaunchPlan()
+    rc = L.lib().det6d_mlp_group3_plan(c1, c2, c3, ns, b, m, compact, capacity, plan)
+    assert rc in (0, -1)
+    plan.name = L.GROUP_ROUTES[plan.route] if rc == 0 else None
+    return rc == 0, plan
+
+
+def geometry(plan):
+    return (plan.name, plan.tile_rows, plan.grid_x, plan.grid_y, plan.block, plan.lds_bytes)
+
+
+def test_launch_plans_pin_the_routes_and_their_geometry():
+    """Every route of the three fused MLP entry points with the launch geometry the launchers computed inline before the plan
+    functions existed; each expectation is a literal with the formula of that code."""
+    sa1 = [rows_stack(96, 64, 32, 1)]
+    # W: LDS 4 * ((64 + 32) * 32 + 4 * 32 * 97) = 61 952; one wave per 32-row tile, four per workgroup: 16384 / 32 / 4 = 128 (cap 512)
+    assert geometry(rows_plan(16384, sa1)[1]) == ('W', 32, 128, 1, 256, 61952)
+    # R (rows % 32 != 0): LDS 4 * (2 * 64 * 97 + 64 * 65) = 66 304; 64-row tiles: ceil(16400 / 64) = 257 (cap 512)
+    assert geometry(rows_plan(16400, sa1)[1]) == ('R', 64, 257, 1, 256, 66304)
+    assert rows_plan(16384, sa1, aligned=0)[1].name == 'G2' and rows_plan(16352, sa1)[1].name == 'G1'   # W, R: 16-byte rows, >= 16384 of them
+    # G1, the shape of the launcher bug: 32-row tiles take 4 * 32 * (641 + 65) = 90 368 bytes, 64-row tiles (180 736) do not
+    # fit 163 840; one workgroup per CU by LDS: min(16384 / 32, 256 * 1) = 256
+    assert geometry(rows_plan(16384, [rows_stack(640, 64, 3)])[1]) == ('G1', 32, 256, 1, 256, 90368)
+    # GC: the input in chunks of 256 columns: 4 * 32 * (257 + 129) = 49 408 bytes, 3 per CU; two chains: cap 256 * 3 / 2 = 384
+    towers = [rows_stack(512, 128, 1), rows_stack(512, 128, 32)]
+    assert geometry(rows_plan(225, towers)[1]) == ('GC', 32, 8, 2, 256, 49408)              # ceil(225 / 32) = 8
+    assert geometry(rows_plan(16384, towers)[1]) == ('GC', 32, 384, 2, 256, 49408)          # min(512, 384)
+    # G2: 64-row tiles: 4 * 64 * (65 + 65) = 33 280 bytes, 4 per CU: min(16384 / 64, 1024) = 256
+    assert geometry(rows_plan(16384, [rows_stack(64, 64, 3)])[1]) == ('G2', 64, 256, 1, 256, 33280)
+    assert geometry(rows_plan(16383, [rows_stack(64, 64, 3)])[1]) == ('G1', 32, 512, 1, 256, 16640)   # below 16384 rows: 32-row tiles
+
+    # chain, WIDE: 512 threads take 8 tiles at a time: min(ceil(tiles / 8), 256); LDS 4 * (70 * 64 + 66 * c2 + 128 * c2)
+    big = dict(b=8, m=4096)                   # 8 * 4096 * 32 rows = 32 768 tiles: every cap is reached
+    for name, lds in (('wide64', 67584), ('wide96', 92416)):
+        w = CHAIN_SETS[name]
+        assert geometry(chain_plan(*w, 16, 2, 96)[1]) == ('WIDE', 32, 12, 1, 512, lds)       # 2 * 96 * 16 / 32 = 96 tiles -> 12
+        assert geometry(chain_plan(*w, 32, 2, 96)[1]) == ('WIDE', 32, 24, 1, 512, lds)       # 192 tiles -> 24
+        assert geometry(chain_plan(*w, 32, **big)[1]) == ('WIDE', 32, 256, 1, 512, lds)
+        assert geometry(chain_plan(*w, 0, 1, 0, 1, 4096)[1]) == ('WIDE', 32, 16, 1, 512, lds)      # compact: 4096 / 32 / 8 = 16
+    # REG: four waves, a tile each: ceil(tiles / 4), dense at most 1024 workgroups, compact lists 2048; no dynamic LDS
+    for name in ('reg16', 'reg32'):
+        r = CHAIN_SETS[name]
+        assert geometry(chain_plan(*r, 16, 2, 96)[1]) == ('REG', 32, 24, 1, 256, 0)          # 96 tiles -> 24
+        assert geometry(chain_plan(*r, 32, **big)[1]) == ('REG', 32, 1024, 1, 256, 0)
+        assert geometry(chain_plan(*r, 0, 1, 0, 1, 4096)[1]) == ('REG', 32, 32, 1, 256, 0)   # compact: 128 tiles -> 32
+        assert geometry(chain_plan(*r, 0, 1, 0, 1, 1 << 20)[1]) == ('REG', 32, 2048, 1, 256, 0)
+    # LDS: run-time widths, or centres of two scenes in a tile of the register kernel (ns = 16, odd m): ceil(tiles / 4), at most 1536
+    assert geometry(chain_plan(*CHAIN_SETS['lds'], 32, 2, 96)[1]) == ('LDS', 32, 48, 1, 256, 0)     # 192 tiles -> 48
+    assert geometry(chain_plan(*CHAIN_SETS['lds'], 32, **big)[1]) == ('LDS', 32, 1536, 1, 256, 0)
+    assert geometry(chain_plan(*CHAIN_SETS['reg16'], 16, 2, 3)[1]) == ('LDS', 32, 1, 1, 256, 0)     # 2 * 3 * 16 / 32 = 3 tiles -> 1
+
+    # group, default settings: the head's sets stream, 4 * (32 * (257 + 2 * 129) + 64 + 4 * 64 * 4 + 4 * 256 + 4) = 74 384 bytes: 2
+    # per CU; SA3's run the one-pass form on four waves: 4 * (32 * (c1 + 1 + c2 + 1) + 64 + 4 * 64 * 2 + 4) = 35 344 (4 per CU) /
+    # 51 728 (3 per CU); a workgroup per 32-row tile, at most 256 x per CU
+    want = {(128, 128, 256): ('ONEPASS4', 35344, 1024), (128, 256, 256): ('ONEPASS4', 51728, 768),
+            (256, 256, 512): ('STREAM', 74384, 512), (256, 512, 1024): ('STREAM', 74384, 512)}
+    for w in GROUP_SETS:
+        route, lds, cap = want[w]
+        assert geometry(group_plan(*w, 32, 2, 96)[1]) == (route, 32, 192, 1, 256, lds)              # 2 * 96 * 32 / 32 = 192 tiles
+        assert geometry(group_plan(*w, 16, 2, 96)[1]) == (route, 32, 96, 1, 256, lds)
+        assert geometry(group_plan(*w, 32, **big)[1]) == (route, 32, cap, 1, 256, lds)
+        assert geometry(group_plan(*w, 0, 1, 0, 1, 4096)[1]) == (route, 32, 128, 1, 256, lds)       # compact: 4096 / 32
+        assert geometry(group_plan(*w, 0, 1, 0, 1, 1 << 20)[1]) == (route, 32, cap, 1, 256, lds)
+        assert geometry(group_plan(*w, 16, 0, 0)[1]) == (route, 32, 0, 1, 256, lds)                 # widths only: no grid
+
+
+def test_launch_plans_hold_their_invariants_over_a_sweep_of_shapes():
+    """Accepted plans fit the CU and have a grid; the refusals that used to surface as a failed launch in the middle of a
+    forward pass are refusals of the plan; the _supported queries are the plan's answer."""
+    import itertools
+    from collections import Counter
+    from de6d_amd import _lib as L
+    seen, refused = Counter(), Counter()
+
+    def check(kind, rows, ok, plan):
+        if not ok:
+            refused[kind] += 1
+            return
+        seen[kind, plan.name] += 1
+        assert plan.lds_bytes <= KB160 and plan.block in (256, 512) and plan.tile_rows in (32, 64) and plan.grid_y in (1, 2), geometry(plan)
+        assert (plan.grid_x >= 1) if rows > 0 else (plan.grid_x == 0), (rows, geometry(plan))
+
+    for depth, k0, last, nchains in itertools.product((1, 2, 3, 4), (32, 96, 256, 512, 640, 992, 1024), (1, 3, 32, 50), (1, 2)):
+        for hidden in itertools.product((32, 64, 128, 256), repeat=depth - 1):
+            for rows in (0, 1, 225, 16384, 16400):
+                ok, plan = rows_plan(rows, [rows_stack(k0, *hidden, last)] * nchains)
+                check('rows', rows, ok, plan)
+                # two activation buffers of a 32-row tile: the input (or its 256-column chunks) / the widest even-layer input, the widest odd-layer input
+                assert ok == (k0 < 1024 or (k0 == 1024 and hidden[:1] in ((32,), (64,), (128,)) or (depth == 1 and last <= 128))), (k0, hidden, last)
+    assert not rows_plan(16384, [rows_stack(1024, 256, 32)])[0]
+    assert not rows_plan(64, [rows_stack(96, 64, 1)], ldx=100, xcol0=8)[0] and rows_plan(64, [rows_stack(96, 64, 1)], ldx=104, xcol0=8)[0]
+
+    sets = list(CHAIN_SETS.values()) + [(l, c1, c2, c3) for l in (4, 5, 8, 12, 68) for c1, c2, c3 in ((16, 16, 32), (64, 64, 64), (33, 32, 64))]
+    for (lda, c1, c2, c3), ns, b, m in itertools.product(sets, (8, 16, 32), (1, 2), (1, 2, 3, 6, 96)):
+        ok, plan = chain_plan(lda, c1, c2, c3, ns, b, m)
+        check('chain', b * m * ns, ok, plan)
+        narrow = lda in (4, 8) and c1 <= 32 and c2 <= 32 and c3 <= 64
+        wide = (lda, c1, c3) == (68, 64, 128) and c2 in (64, 96)
+        assert ok == (ns in (16, 32) and b * m * ns % 32 == 0 and (narrow or (wide and (ns == 32 or m % 2 == 0)))), (lda, c1, c2, c3, ns, b, m)
+        if ok and not wide:
+            reg = lda == 4 and (c1, c2, c3) in ((16, 16, 32), (32, 32, 64)) and (ns == 32 or m % 2 == 0)
+            assert plan.name == ('REG' if reg else 'LDS')
+        okc, planc = chain_plan(lda, c1, c2, c3, ns, 1, m, 1, 128 * m)          # the compact entry: register kernels only
+        check('chain', 128 * m, okc, planc)
+        assert okc == (wide or (lda == 4 and (c1, c2, c3) in ((16, 16, 32), (32, 32, 64)))) and (not okc or planc.name in ('WIDE', 'REG'))
+        assert chain_plan(lda, c1, c2, c3, ns, 0, 0)[0] == (ns in (16, 32) and (narrow or wide))      # the widths alone
+        assert not chain_plan(lda, c1, c2, c3, ns, 1, m, 1, 128 * m + 32)[0]
+    # the refusals by name: a wide chain / any chain whose tiles would pair centres of two scenes or split a tile
+    for w in ('wide64', 'wide96'):
+        assert not chain_plan(*CHAIN_SETS[w], 16, 1, 3)[0] and not chain_plan(*CHAIN_SETS[w], 16, 2, 3)[0] and chain_plan(*CHAIN_SETS[w], 16, 1, 6)[0]
+    assert not chain_plan(*CHAIN_SETS['reg16'], 16, 1, 3)[0] and not chain_plan(5, 16, 16, 32, 32, 1, 2)[0]
+
+    for (c1, c2, c3), ns, b, m, compact in itertools.product(GROUP_SETS + [(128, 128, 128), (256, 512, 512)], (8, 16, 32), (1, 2), (1, 2, 3), (0, 1)):
+        ok, plan = group_plan(c1, c2, c3, ns, b, m, compact, 128 * m)
+        check('group', 128 * m if compact else b * m * ns, ok, plan)
+        assert ok == ((c1, c2, c3) in GROUP_SETS and (compact == 1 or (ns in (16, 32) and (ns == 32 or m % 2 == 0)))), (c1, c2, c3, ns, b, m, compact)
+        widths_only = (c1, c2, c3) in GROUP_SETS and (compact == 1 or ns in (16, 32))
+        assert group_plan(c1, c2, c3, ns, 0, 0, compact)[0] == widths_only == bool(L.lib().det6d_mlp_group3_supported(c1, c2, c3, ns, compact))
+    assert not group_plan(128, 128, 256, 16, 2, 3)[0] and not group_plan(128, 128, 256, 0, 1, 0, 1, 96)[0]
+
+    # not vacuous: every route the shipped settings can take was accepted somewhere, every entry point refused something
+    for key in [('rows', r) for r in L.ROWS_ROUTES] + [('chain', r) for r in L.CHAIN_ROUTES] + [('group', 'STREAM'), ('group', 'ONEPASS4')]:
+        assert seen[key] >= 1, (key, seen)
+    assert all(refused[k] >= 1 for k in ('rows', 'chain', 'group')), refused
+
+
+def test_route_switches_are_read_by_the_plan_functions():
+    """the experiments build's route switches reach the launch through the plan: eight waves per tile for the head's groups once
+    their streaming form is off, no wide chain kernel on either entry with DET6D_CHAIN_NO_WIDE (switches are read once per
+    process: a child)"""
+    import subprocess
+    import sys
+    from de6d_amd import _build
+    _build.build(experiments=True)
+    code = ("from tests.test_host_logic import chain_plan, group_plan, geometry, CHAIN_SETS\n"
+            "w = CHAIN_SETS['wide64']\n"
+            "print(geometry(group_plan(256, 512, 1024, 32, 2, 96)[1]), geometry(group_plan(128, 256, 256, 32, 2, 96)[1]),"
+            " chain_plan(*w, 32, 2, 96)[0], chain_plan(*w, 0, 1, 0, 1, 4096)[0], chain_plan(*CHAIN_SETS['reg16'], 32, 2, 96)[1].name)")
+    env = dict(os.environ, DET6D_EXPERIMENTS_LIB='1', DET6D_GROUP_STREAM='0', DET6D_CHAIN_NO_WIDE='1', DET6D_CHAIN_LDS='1')
+    out = subprocess.run([sys.executable, '-c', code], env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr
+    # one-pass, eight waves: 4 * (32 * (257 + 513) + 64 + 8 * 64 * 4 + 4) = 107 024 bytes, one workgroup per CU; SA3 stays at four
+    assert out.stdout.strip() == "('ONEPASS8', 32, 192, 1, 512, 107024) ('ONEPASS4', 32, 192, 1, 256, 51728) False False LDS", out.stdout
+
+
+def test_fused_predicates_ask_the_plan():
+    """fused.chain_eligible / group_kernel_eligible at a (b, m): what the library would refuse is not offered to it"""
+    from de6d_amd.ops import fused
+    layers = lambda *c: [(None, None, n, 1) for n in c]   # noqa: E731
+    wide, narrow = layers(64, 64, 128), layers(16, 16, 32)
+    assert not fused.chain_eligible(68, wide, 16, b=1, m=3) and not fused.chain_eligible(4, narrow, 16, b=1, m=3)
+    assert fused.chain_eligible(68, wide, 16, b=1, m=6) and fused.chain_eligible(4, narrow, 16, b=1, m=6)
+    assert fused.chain_eligible(68, wide, 16) and fused.chain_eligible(68, layers(64, 96, 128), 32) and fused.chain_eligible(8, layers(24, 32, 40), 32)
+    assert not fused.chain_eligible(8, narrow, 8) and not fused.chain_eligible(12, narrow, 16) and not fused.chain_eligible(5, narrow, 16)
+    assert not fused.chain_eligible(4, narrow[:2], 16) and not fused.chain_eligible(4, [(None, None, 16, 0)] + narrow[1:], 16)
+    assert fused.chain_compact_eligible(68, wide) and fused.chain_compact_eligible(4, narrow) and not fused.chain_compact_eligible(8, narrow)
+    group = layers(128, 128, 256)
+    assert fused.group_kernel_eligible(group, 16, False) and fused.group_kernel_eligible(group, 16, False, b=1, m=2)
+    assert not fused.group_kernel_eligible(group, 16, False, b=1, m=3) and fused.group_kernel_eligible(group, 16, True, b=1, m=3)
+    assert not fused.group_kernel_eligible(layers(128, 128, 128), 16, False) and not fused.group_kernel_eligible(group, 8, False)
+
+
 def test_bench_refuses_more_ranks_than_devices():
     """`bench.py --gpus N` with fewer than N visible devices exits non-zero BEFORE any rank is started or any rendezvous is
     attempted (a rank that left alone would keep the others waiting for the store's ten-minute time-out); decided from

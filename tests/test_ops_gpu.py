@@ -575,13 +575,9 @@ def test_ball_query_grid_dense_shells(ext, oracle_ops):
             np.testing.assert_array_equal(ib.cpu().numpy(), oib)
 
 
-@pytest.mark.parametrize("c_in,widths,ns", [(1, (16, 16, 32), 16), (1, (32, 32, 64), 32), (4, (24, 32, 40), 16), (1, (8, 16, 16), 32),
-                                             (64, (64, 64, 128), 16), (64, (64, 96, 128), 32), (64, (64, 96, 128), 16), (64, (64, 64, 128), 32)])
-def test_mlp_chain3_equals_three_linears(ext, oracle_ops, c_in, widths, ns):
-    """the fused narrow-MLP launch against the oracle's three-layer sequence (and hence against three
-    det6d_linear calls, which test_linear_* pins to the same oracle)"""
-    fused = ext[2]
-    b, n, m = 2, 700, 96
+def chain3_case(oracle_ops, c_in, widths, ns, b, n, m, sentinel=0.0):
+    """one grouped three-layer MLP: (rows, idx, ctr, cnt) on the host, the layers on the device, and the oracle's three-layer
+    sequence pooled into columns 3.. of a (b * m, widths[2] + 3) array pre-filled with `sentinel`"""
     rng = np.random.default_rng(sum(widths))
     ld = (3 + c_in + 3) // 4 * 4
     rows = np.zeros((b, n, ld), np.float32)
@@ -599,15 +595,104 @@ def test_mlp_chain3_equals_three_linears(ext, oracle_ops, c_in, widths, ns):
         s = rng.normal(size=(dims[i + 1],)).astype(np.float32)
         layers_np.append((w, s))
         layers_dev.append((dev(w), dev(s), dims[i + 1], 1))
-    assert fused.chain_eligible(ld, layers_dev, ns)
-    out = torch.zeros((b * m, widths[2] + 3), device="cuda")
-    fused.mlp_chain3(dev(rows), dev(idx), dev(ctr), dev(cnt), layers_dev, out, 3)
     h = oracle_ops.linear(rows, layers_np[0][0], layers_np[0][1], 1, idx=idx, ctr=ctr)
     h = oracle_ops.linear(np.ascontiguousarray(np.pad(h, ((0, 0), (0, layers_np[1][0].shape[0] - h.shape[1])))), layers_np[1][0], layers_np[1][1], 1)
     h = np.ascontiguousarray(np.pad(h[:, :widths[1]], ((0, 0), (0, layers_np[2][0].shape[0] - widths[1]))))
-    ref = np.zeros((b * m, widths[2] + 3), np.float32)
+    ref = np.full((b * m, widths[2] + 3), sentinel, np.float32)
     oracle_ops.linear(h, layers_np[2][0][:, :widths[2]], layers_np[2][1], 1, cnt=cnt, pool=ns, out=ref, col0=3)
+    return ld, rows, idx, ctr, cnt, layers_dev, ref
+
+
+@pytest.mark.parametrize("c_in,widths,ns", [(1, (16, 16, 32), 16), (1, (32, 32, 64), 32), (4, (24, 32, 40), 16), (1, (8, 16, 16), 32),
+                                             (64, (64, 64, 128), 16), (64, (64, 96, 128), 32), (64, (64, 96, 128), 16), (64, (64, 64, 128), 32)])
+def test_mlp_chain3_equals_three_linears(ext, oracle_ops, c_in, widths, ns):
+    """the fused narrow-MLP launch against the oracle's three-layer sequence (and hence against three
+    det6d_linear calls, which test_linear_* pins to the same oracle)"""
+    fused = ext[2]
+    b, n, m = 2, 700, 96
+    ld, rows, idx, ctr, cnt, layers_dev, ref = chain3_case(oracle_ops, c_in, widths, ns, b, n, m)
+    assert fused.chain_eligible(ld, layers_dev, ns)
+    out = torch.zeros((b * m, widths[2] + 3), device="cuda")
+    fused.mlp_chain3(dev(rows), dev(idx), dev(ctr), dev(cnt), layers_dev, out, 3)
     np.testing.assert_array_equal(out.cpu().numpy(), ref)
+
+
+SENT = -7.0
+
+
+@pytest.mark.parametrize("c_in,widths", [(1, (16, 16, 32)), (4, (24, 32, 40)), (64, (64, 64, 128)), (64, (64, 96, 128))])
+def test_chain_launch_accepts_exactly_what_its_plan_accepts(ext, oracle_ops, c_in, widths):
+    """det6d_mlp_chain3 returns DET6D_OK exactly for the (b, m, ns) det6d_mlp_chain3_plan accepts — the launch routes by the
+    function the query answers from — over the row counts at which the routes part: odd m with ns = 16 (two centres of a
+    32-row tile in different scenes: LDS kernel for the narrow widths, refusal for the wide ones) and b * m * ns off the tiles.
+    Accepted: the oracle's three layers bit for bit around an untouched sentinel; refused (a status before any launch): the
+    sentinel everywhere."""
+    fused = ext[2]
+    L, n = fused.L, 64
+    accepted = 0
+    for b, m, ns in [(b, m, ns) for b in (1, 2) for m in (1, 2, 3, 6) for ns in (16, 32)]:
+        ld, rows, idx, ctr, cnt, layers, ref = chain3_case(oracle_ops, c_in, widths, ns, b, n, m, SENT)
+        plan = L.LaunchPlan()
+        ok = L.lib().det6d_mlp_chain3_plan(ld, *widths, ns, b, m, 0, 0, plan) == 0
+        assert fused.chain_eligible(ld, layers, ns, b, m) == ok
+        out = torch.full((b * m, widths[2] + 3), SENT, device="cuda")
+        d_rows, d_idx, d_ctr, d_cnt = dev(rows), dev(idx), dev(ctr), dev(cnt)
+        (w1, s1, c1, _), (w2, s2, c2, _), (w3, s3, c3, _) = layers
+        rc = L.lib().det6d_mlp_chain3(b * m * ns, n, m, ns, L.ptr(d_rows), ld, L.ptr(d_idx), L.ptr(d_ctr), 3, L.ptr(d_cnt), L.ptr(w1),
+                                      w1.shape[1], L.ptr(s1), c1, L.ptr(w2), w2.shape[1], L.ptr(s2), c2, L.ptr(w3), w3.shape[1], L.ptr(s3),
+                                      c3, L.ptr(out), out.shape[1], 3, L.stream_ptr())
+        assert rc == (0 if ok else -1), (b, m, ns, rc, L.CHAIN_ROUTES[plan.route] if ok else None)
+        np.testing.assert_array_equal(out.cpu().numpy(), ref if ok else np.full_like(ref, SENT), err_msg=str((b, m, ns)))
+        accepted += ok
+    assert 0 < accepted < 16
+
+
+@pytest.mark.parametrize("b,m", [(1, 2), (2, 2), (1, 3), (2, 3)])
+def test_group_launch_accepts_exactly_what_its_plan_accepts(ext, oracle_ops, b, m):
+    """the same for det6d_mlp_group3 on dense rows, (128, 128, 256) with ns = 16: even m runs (== the oracle's expand + two
+    linears), odd m is refused by plan and launch alike"""
+    from tests.test_compact_gpu import make_layers, padded_query
+    fused = ext[2]
+    L, n, ns, c_in, widths = fused.L, 64, 16, 128, (128, 128, 256)
+    rng = np.random.default_rng(m)
+    ld = (3 + c_in + 3) // 4 * 4
+    rows = np.zeros((b, n, ld), np.float32)
+    rows[..., :3 + c_in] = rng.normal(size=(b, n, 3 + c_in))
+    ctr = rng.normal(size=(b, m, 3)).astype(np.float32)
+    cnt, idx = padded_query(rng, b, n, m, ns)
+    layers_np, layers = make_layers(rng, ld, c_in, widths)
+    ok = L.lib().det6d_mlp_group3_plan(*widths, ns, b, m, 0, 0, L.LaunchPlan()) == 0
+    assert ok == (m % 2 == 0) == fused.group_kernel_eligible(layers, ns, False, b, m)
+    ref = np.full((b * m, widths[2] + 4), SENT, np.float32)
+    if ok:
+        h = oracle_ops.linear(rows, layers_np[0][0], layers_np[0][1], 1, idx=idx, ctr=ctr)
+        h = oracle_ops.linear(h, layers_np[1][0], layers_np[1][1], 1)
+        oracle_ops.linear(h, layers_np[2][0][:, :widths[2]], layers_np[2][1], 1, cnt=cnt, pool=ns, out=ref, col0=4)
+    d_rows, d_ctr, d_idx, d_cnt = dev(rows), dev(ctr), dev(idx), dev(cnt)
+    wz = layers[0][0].clone()
+    wz[:3] = 0
+    p = torch.empty((b * n, wz.shape[1]), device="cuda")
+    fused.linear(d_rows.view(b * n, ld), wz, None, 0, p)
+    out = torch.full((b * m, widths[2] + 4), SENT, device="cuda")
+    (w1, s1, c1, _), (w2, s2, c2, _), (w3, s3, c3, _) = layers
+    rc = L.lib().det6d_mlp_group3(b * m * ns, L.ptr(p), p.shape[1], 0, L.ptr(w1), w1.shape[1], L.ptr(s1), c1, L.ptr(w2), w2.shape[1],
+                                  L.ptr(s2), c2, L.ptr(w3), w3.shape[1], L.ptr(s3), c3, L.ptr(d_rows), ld, L.ptr(d_ctr), 3, L.ptr(d_idx), n,
+                                  m, ns, L.ptr(d_cnt), None, None, None, L.ptr(out), out.shape[1], 4, L.stream_ptr())
+    assert rc == (0 if ok else -1)
+    np.testing.assert_array_equal(out.cpu().numpy(), ref)
+
+
+def test_sa_layer_runs_the_shapes_the_chain_kernels_refuse():
+    """dense rows, lda = 68, nsample 16 and THREE caller-supplied centres: the wide chain kernel pairs two centres per tile and
+    refuses an odd m; forward_rows asks the plan at its (b, m) and takes the per-layer route (it used to offer the shape to the
+    launch, which raised).  == the oracle's layer, bit for bit.  (DET6D_DENSE_ROWS is read at import: a child process.)"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, 'tests', 'gpu_scripts', 'sa_odd_centres.py')],
+                         env=dict(os.environ, DET6D_DENSE_ROWS='1'), cwd=root, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    assert 'sa_odd_centres ok' in out.stdout
 
 
 def test_fallback_kernels_via_env_switches(tmp_path):

@@ -211,6 +211,10 @@ _EXT_SIGNATURES = {
     "det6d_ext_corner_loss": [c_int, _P, c_int, _P, c_int, _P, _P],
     "det6d_ext_linear_backward": [c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int,
                                   _P, c_int, _P, _P, c_int64, _P],
+    "det6d_ext_group_gather": [c_int, c_int, c_int, c_int, _P, c_int, c_int, _P, _P, c_int, _P, c_int, _P],
+    "det6d_ext_group_pool_backward": [c_int, c_int, c_int, _P, c_int, _P, _P, c_int, c_int, _P, c_int, _P],
+    "det6d_ext_group_centre_grad": [c_int, c_int, _P, c_int, _P, c_int, _P],
+    "det6d_ext_vote_backward": [c_int, _P, c_int, c_float, c_float, c_float, _P, c_int, _P, c_int, _P],
 }
 #: every symbol include/det6d_ext.h declares (tests/test_ext_boundary.py checks the export table)
 EXT_EXPORTED_SYMBOLS = sorted(list(_EXT_SIGNATURES) + ["det6d_ext_version", "det6d_ext_last_error",

@@ -22,10 +22,16 @@ Fine-tuning the towers: prepare_loss(batch_dict, requires_grad=True, towers=True
 reg_layers from the pooled vote features through ops.mlp_backward.FoldedChain (the forward kernels and the cached folded
 tensors of the eval forward: the same bits), so that loss.backward() leaves .grad on every parameter of the three stacks
 (conv.weight, bn.weight, bn.bias, the last conv.bias) and dL/d(pooled features) on forward_ret_dict['point_pooled_features'].
-BatchNorm stays frozen (eval mode: the reference's model.eval() plus grad).  vote_layers and everything before the pooled
-features get NO gradient: the true gradient of the vote coordinates also flows through the SA layer around the votes (grouped
-xyz - new_xyz), a path that does not exist here, and a vote-FC gradient from d_vote alone would silently differ from the
-reference's.  BatchNorm with batch statistics and a training-mode forward() stay out of scope.
+BatchNorm stays frozen (eval mode: the reference's model.eval() plus grad).  With towers=True alone, vote_layers and everything
+before the pooled features get NO gradient: the true gradient of the vote coordinates also flows through the SA layer around the
+votes (grouped xyz - new_xyz), and a vote-FC gradient from d_vote alone would silently differ from the reference's.
+Fine-tuning the whole head: prepare_loss(batch_dict, requires_grad=True, head=True) also re-evaluates vote_layers, the clamp and
+the SA layer around the votes (ops.group_backward: VotePoints, GroupedChain; the ball queries re-run on the vote coordinates,
+their membership a constant), so that loss.backward() leaves .grad on every parameter of vote_layers, SA_module.mlps and the
+three stacks: the vote coordinates collect the loss's own d_vote and the d(new_xyz) of every radius group.  At a vote offset
+exactly on its clamp bound the whole gradient passes (torch's max / min backward passes half).
+The gradient with respect to the input points' features and coordinates (the backbone), BatchNorm with batch statistics and a
+training-mode forward() stay out of scope.
 Differences from the reference, all of them kept on purpose:
   * tb_dict values are 0-d device tensors, not Python floats: nothing is read on the host, the call can be captured;
   * labels are constants.  The reference has no detach at :310, so a gradient leaks from the encoded offset labels back into
@@ -49,8 +55,8 @@ import torch.nn as nn
 
 from ...ops.pointnet2.pointnet2_batch import pointnet2_modules
 from ...ops.pointnet2.pointnet2_batch.pointnet2_modules import fold_sequential, rows_ld, round4, run_chain, to_device
-from ...ops_backend import fused
-from ....ops import box_targets, head_loss, mlp_backward
+from ...ops_backend import fused, pointnet2_batch_hip as pn2
+from ....ops import box_targets, group_backward, head_loss, mlp_backward
 from ...utils import box_coder_utils
 
 
@@ -200,7 +206,8 @@ class PointHeadBox6DVote(nn.Module):
         batch_dict['point_reg_preds'] = point_reg_preds
         self.forward_ret_dict = {'batch_size': batch_size, 'point_cls_preds': point_cls_preds,
                                  'point_reg_preds': point_reg_preds, 'point_box_preds': boxes,
-                                 'point_pooled_features': pooled}        # a reference: prepare_loss(towers=True) starts here
+                                 'point_pooled_features': pooled,        # a reference: prepare_loss(towers=True) starts here
+                                 'xyz': xyz, 'rows': rows, 'cand_rows': cand_rows}       # references: prepare_loss(head=True)
         return batch_dict
 
     # ---- target assignment (point_head_box6d_vote.py:171-326, :387-407) ------------------------------------------------
@@ -354,7 +361,7 @@ class PointHeadBox6DVote(nn.Module):
         spec, tensors = self._loss_inputs()
         return head_loss.forward(spec, *(t.detach().contiguous() for t in tensors), per_point=True)
 
-    def prepare_loss(self, batch_dict, requires_grad=False, towers=False):
+    def prepare_loss(self, batch_dict, requires_grad=False, towers=False, head=False):
         """Fills forward_ret_dict with what the reference's training forward puts there (:823-876), for the batch_dict an eval
         forward returned plus batch_dict['gt_boxes'] (B, M, 9 + 1): the five labels of assign_training_targets,
         point_candidate_coords and point_vote_coords as (N, 3), beside the predictions forward() left.
@@ -363,20 +370,42 @@ class PointHeadBox6DVote(nn.Module):
         towers=True re-evaluates shared_fc_layer, cls_layers and reg_layers from point_pooled_features (made a leaf) with a graph
         to their parameters and stores those predictions — the bits of the eval forward — in place of the leaves: backward()
         then leaves .grad on every parameter of the three stacks and on point_pooled_features; point_vote_coords stays a
-        leaf, vote_layers and the backbone get nothing (see the module docstring)."""
+        leaf, vote_layers and the backbone get nothing (see the module docstring).
+        head=True implies the towers' graph and re-evaluates what lies before it as well, from the references forward() kept
+        (xyz, rows, cand_rows): vote_layers, the clamp, the ball queries around the votes (constants) and SA_module.mlps.
+        point_vote_coords is then the (N, 3) view of the re-evaluated votes, a non-leaf in which the loss's d_vote and the SA
+        layer's d(new_xyz) add up, and point_pooled_features the re-evaluated tensor — all of them the bits of the eval
+        forward.  backward() leaves .grad on every parameter of the head; the backbone gets nothing."""
         ret = self.forward_ret_dict
         if ret is None or 'point_reg_preds' not in ret:
             raise RuntimeError("prepare_loss needs the forward_ret_dict of an eval forward")
+        towers = towers or head
         if towers and self.training:
             raise RuntimeError("the HIP head folds BatchNorm: call .eval() first")
+        if head:
+            for key in ('xyz', 'rows', 'cand_rows'):
+                if key not in ret:
+                    raise RuntimeError("prepare_loss(head=True) needs forward_ret_dict['%s'] of an eval forward" % key)
         ret.update(self.assign_training_targets(batch_dict))
         ret['point_candidate_coords'] = batch_dict['point_candidate_coords'][:, 1:4].contiguous()
         ret['point_vote_coords'] = batch_dict['point_vote_coords'][:, 1:4].contiguous()
         for key in ('point_vote_coords', 'point_cls_preds', 'point_reg_preds'):
             ret[key] = ret[key].detach().requires_grad_(requires_grad)
-        if towers:
-            pooled = ret['point_pooled_features'].detach().requires_grad_(requires_grad)
+        if head:
+            # Let go of the previous step's graph BEFORE the new one is built: the pooled tensor of an earlier head=True call is
+            # a non-leaf, and while it lives the AccumulateGrad nodes of vote_layers and SA_module.mlps live too and are reused
+            # — with the stream of the step that created them.  A step captured on another stream would then make autograd
+            # synchronise the capture stream with that stream: a fork onto the default stream inside the capture.
+            ret['point_pooled_features'] = ret['point_pooled_features'].detach()
+            with torch.set_grad_enabled(requires_grad):
+                vote, pooled = self._reevaluate_votes(ret)
+            ret['point_vote_coords'] = vote.view(-1, 3)
             ret['point_pooled_features'] = pooled
+        if towers:
+            pooled = ret['point_pooled_features']
+            if not head:
+                pooled = pooled.detach().requires_grad_(requires_grad)
+                ret['point_pooled_features'] = pooled
             f = self._prepare(pooled.device)
             k0 = sum(seq[-3].out_channels for seq in self.SA_module.mlps)
             with torch.set_grad_enabled(requires_grad):
@@ -385,6 +414,37 @@ class PointHeadBox6DVote(nn.Module):
                 cls, reg = mlp_backward.folded_chain(pooled.view(-1, pooled.shape[-1]), chains[0], chains[1:], k0=k0)
             ret['point_cls_preds'], ret['point_reg_preds'] = cls, reg
         return ret
+
+    def _reevaluate_votes(self, ret):
+        """vote_layers -> clamp -> ball queries -> SA_module.mlps -> max-pool, dense and layer by layer, with a graph to the
+        parameters -> (vote (B, P, 3), pooled (B, P, round4(sum C))): the bits forward() computed on its fused routes"""
+        sa = self.SA_module
+        if sa.dilated_radius_group or sa.pool_method != 'max_pool' or sa.skip_connection:
+            raise NotImplementedError("prepare_loss(head=True): dilated groups, pooling other than max_pool and skip connections "
+                                      "have no backward")
+        xyz, rows, cand_rows = ret['xyz'], ret['rows'], ret['cand_rows']
+        f, f_sa = self._prepare(rows.device), sa._prepare(rows.device)
+        b, p, ld = cand_rows.shape
+        # the whole candidate rows enter the first layer: the folded weight's three coordinate rows are zero (their dW reaches
+        # no parameter) — run_chain(cand_rows, f['vote']) of forward()
+        vote_chain = mlp_backward.folded_params(self.vote_layers, f['vote'], k_offset=3)
+        off, = mlp_backward.folded_chain(cand_rows.view(b * p, ld), vote_chain)
+        vote = group_backward.VotePoints.apply(off, cand_rows, tuple(self.vote_cfg.MAX_TRANSLATION_RANGE))
+        centres = vote.detach()
+        shells = [(0.0, radius, nsample) for radius, nsample in zip(sa.radii, sa.nsamples)]
+        if len(shells) == 2:
+            ca, ia, cb, ib = fused.ball_query_pair(xyz, centres, shells[0], shells[1])
+            found = [(ca, ia), (cb, ib)]
+        else:
+            found, n = [], xyz.shape[1]
+            for _, radius, nsample in shells:
+                cnt = torch.zeros((b, p), dtype=torch.int32, device=xyz.device)
+                idx = torch.zeros((b, p, nsample), dtype=torch.int32, device=xyz.device)
+                pn2.ball_query_cnt_wrapper(b, n, p, radius, nsample, centres, xyz, cnt, idx)
+                found.append((cnt, idx))
+        groups = [mlp_backward.folded_params(seq, layers) for seq, layers in zip(sa.mlps, f_sa['groups'])]
+        pooled = group_backward.grouped_chain(rows, vote, found, groups, f_sa['pooled_width'])
+        return vote, pooled.view(b, p, -1)
 
     def get_vote_layer_loss(self, tb_dict=None):
         """:426-446 -> (vote_loss_reg, tb_dict); tb_dict['vote_loss_reg'] is a 0-d device tensor"""

@@ -1,7 +1,7 @@
 """Det6D detector (core/pcdet/models/detectors/det6d.py:4-30): backbone_3d -> point_head ->
 post_processing.  forward() is inference only.  get_training_loss(batch_dict) (:24-30) gives the point head's loss for the
-batch_dict of an eval forward plus gt_boxes; with towers=True its backward reaches the parameters of the head's three FC stacks
-(PointHeadBox6DVote.prepare_loss).  The backward of everything before the pooled vote features is out of scope."""
+batch_dict of an eval forward plus gt_boxes; with towers=True its backward reaches the parameters of the head's three FC stacks,
+with head=True every parameter of the head (PointHeadBox6DVote.prepare_loss).  The backward of the backbone is out of scope."""
 from ...ops_backend import fused
 from .detector3d_template import Detector3DTemplate
 
@@ -28,13 +28,13 @@ class Det6D(Detector3DTemplate):
             batch_dict = module(batch_dict)
         return self.post_processing_async(batch_dict)
 
-    def get_training_loss(self, batch_dict, requires_grad=False, towers=False):
+    def get_training_loss(self, batch_dict, requires_grad=False, towers=False, head=False):
         """(loss, tb_dict, disp_dict) of :24-30 for the batch_dict forward() or forward_async() filled, plus
         batch_dict['gt_boxes'] (B, M, 9 + 1).  The reference reads the labels its training forward stored; here
         PointHeadBox6DVote.prepare_loss assigns them first.  loss and the tb_dict values are 0-d device tensors; nothing is
-        read on the host.  requires_grad / towers: as prepare_loss takes them (towers=True: loss.backward() leaves .grad on the
-        parameters of shared_fc_layer, cls_layers and reg_layers)."""
+        read on the host.  requires_grad / towers / head: as prepare_loss takes them (towers=True: loss.backward() leaves .grad on
+        the parameters of shared_fc_layer, cls_layers and reg_layers; head=True: on those of vote_layers and SA_module.mlps too)."""
         disp_dict = {}
-        self.point_head.prepare_loss(batch_dict, requires_grad=requires_grad, towers=towers)
+        self.point_head.prepare_loss(batch_dict, requires_grad=requires_grad, towers=towers, head=head)
         loss_point, tb_dict = self.point_head.get_loss()
         return loss_point, tb_dict, disp_dict

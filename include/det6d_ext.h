@@ -233,6 +233,51 @@ int det6d_ext_linear_backward(int rows, int k, int n,
         float *dshift,                          /* (n) column sums of dz, or NULL                                       */
         void *workspace, long long workspace_bytes, det6d_stream_t stream);
 
+/* ------------------------------------------------------------------ grouped-MLP backward */
+
+/* The parts of the backward pass of a grouped MLP (a radius group of a set-abstraction layer, pointnet2_modules.py:305-312 as the
+ * vote head uses it, point_head_box6d_vote.py:815-821, :846) that are not a GEMM.  With idx (b, m, ns) and cnt (b, m) the ball
+ * query's padded lists — constants: ball membership carries no gradient — the forward is
+ *   X0[(c, s)] = [pts[idx[c][s]][0..3) - ctr[c] | pts[idx[c][s]][3..k)];  Y = the pointwise layers of X0 (det6d_linear);
+ *   pooled[c][j] = (cnt[c] > 0) * max_s Y[(c, s)][j],
+ * and its backward is det6d_ext_linear_backward per layer between the four entry points below (the points' own coordinates and
+ * features are constants; the centres are not).  Executable model: tests/models/group_backward.py.
+ * Each entry point is a pure function of its inputs: no floating-point atomics, no counters, nothing depends on the grid; all
+ * stores are ordinary vector stores; asynchronous on `stream`; a bad argument returns DET6D_EINVAL with a message naming the
+ * entry point before anything is launched; with zero rows nothing is launched.
+ * Limits: groups * ns = b * m * ns <= 2^24, 1 <= ns <= 128, 1 <= c <= 4096, 3 <= k <= 4096.
+ *
+ * det6d_ext_group_gather: X0 as a matrix.  out[((bi * m + c) * ns + s)][a] = pts[bi][idx[bi][c][s]][a] - ctr[bi * m + c][a] for
+ *   a < 3: ONE fp32 subtract, the one the forward's gather does; columns [3, k) are copied; columns [k, ldout) are zero-filled, so
+ *   that `out` feeds det6d_linear and det6d_ext_linear_backward as it is.  pts (b, n, ldp), k <= ldp; ctr (b * m, ldctr),
+ *   ldctr >= 3; out follows the rules of det6d_linear's a: ldout % 4 == 0, k <= ldout <= 8192, 16-byte aligned.  An idx outside
+ *   [0, n) is the caller's error, as in det6d_linear mode 1.  16-byte accesses where ldp % 4 == 0 and pts is 16-byte aligned.
+ *
+ * det6d_ext_group_pool_backward: the mask, the max-pool and the last layer's ReLU.  For group r and channel j < c, with
+ *   win = the LOWEST slot s whose y[r * ns + s][j] equals the maximum over all ns slots (the tie rule is part of the contract;
+ *   the padding slots s >= cnt repeat earlier hits with identical bits, so a winner is always a real hit):
+ *     dz[r * ns + s][j] = (s == win && cnt[r] > 0 && y[r * ns + win][j] > 0) ? g[r][gcol0 + j] : 0.
+ *   Every element of dz[:, 0:c) is written, columns beyond c are left alone.  A channel whose maximum is 0 (or negative) passes
+ *   nothing.  y is the last layer's ReLU output (groups * ns, ldy); a NaN in y is outside the contract.  16-byte accesses
+ *   where c, ldy and lddz are multiples of 4 and y and dz are 16-byte aligned.
+ *
+ * det6d_ext_group_centre_grad: dctr[r][a] = -(((0 + dx[r * ns][a]) + dx[r * ns + 1][a]) + ...), a < 3, fp32 adds in ascending
+ *   slot order; written, not accumulated.  dx (groups * ns, lddx) is the three-column dx of the first layer
+ *   (det6d_ext_linear_backward with k = 3, wrow0 = 0); lddx >= 3, lddctr >= 3.
+ *
+ * det6d_ext_vote_backward: the clamp of vote = candidate + clamp(off, -R, R) (det6d_vote_points):
+ *   doff[r][a] = (-R_a <= off[r][a] && off[r][a] <= R_a) ? dvote[r][a] : 0 for the UNCLAMPED off, a < 3, R = (rx, ry, rz) >= 0.
+ *   A NaN in off gives 0.  At off == +-R exactly the whole gradient passes (torch's max / min backward passes half of it).
+ *   0 <= rows <= 2^24; the three row lengths >= 3.
+ * Every pointer is at least 4-byte aligned. */
+int det6d_ext_group_gather(int b, int n, int m, int ns, const float *pts, int ldp, int k, const int *idx, const float *ctr,
+                           int ldctr, float *out, int ldout, det6d_stream_t stream);
+int det6d_ext_group_pool_backward(int groups, int ns, int c, const float *y, int ldy, const int *cnt, const float *g, int ldg,
+                                  int gcol0, float *dz, int lddz, det6d_stream_t stream);
+int det6d_ext_group_centre_grad(int groups, int ns, const float *dx, int lddx, float *dctr, int lddctr, det6d_stream_t stream);
+int det6d_ext_vote_backward(int rows, const float *off, int ldoff, float rx, float ry, float rz, const float *dvote, int lddvote,
+                            float *doff, int lddoff, det6d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

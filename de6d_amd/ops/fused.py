@@ -16,6 +16,32 @@ LINEAR_EVENTS = None
 LINEAR_REPLAY = None
 
 
+def round4(v):
+    return (v + 3) // 4 * 4
+
+
+def rows_ld(channels):
+    """row stride of a rows tensor carrying `channels` feature channels"""
+    return round4(3 + channels)
+
+
+def _launch(issue, work, replay=None):
+    """issue(): one launch of the GEMM family, with the bookkeeping of the two lists above.  work = (rows or the compact
+    list's header, k, ncols) closes the LINEAR_EVENTS entry; replay = (output, what the closure keeps alive[, tensors every
+    replaying stream needs a copy of]) follows issue in the LINEAR_REPLAY entry (issue(ptr_of) re-issues the launch on a
+    stream's own copies)"""
+    if LINEAR_REPLAY is not None and replay is not None:
+        LINEAR_REPLAY.append((issue,) + replay)
+    if LINEAR_EVENTS is None:
+        issue()
+        return
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    issue()
+    e1.record()
+    LINEAR_EVENTS.append((e0, e1) + work)
+
+
 def pack_points(points, ld):
     """(B*N, 1+3+C) [b,x,y,z,f..] -> rows (B*N, ld) [x,y,z,f..,0..]  (pointnet2_backbone.py:193-224)"""
     L.require_cuda(points)
@@ -124,8 +150,9 @@ def fps_workspace(b, n, device='cuda'):
 def gather_centres(xyz, idx, rows_out=None, zero_from=0, out=None, idx_bias=0):
     """idx may be a column slice of a wider (b, M) index buffer (row stride M)"""
     L.require_cuda(xyz, rows_out, out)
-    if not idx.is_cuda or idx.stride(1) != 1:
+    if idx.stride(1) != 1:
         raise L.Det6dError("gather_centres: idx must be a device tensor with unit column stride")
+    L.require_cuda(idx[0])      # (a row of it: the whole of a column slice is not contiguous)
     b, n, _ = xyz.shape
     m = idx.shape[1]
     if out is None:
@@ -250,26 +277,69 @@ def linear(a, w, shift, act, out, k=None, ncols=None, col0=0, idx=None, ctr=None
     g.pool = pool
     g.ncols_pad = ncols_pad      # columns [ncols, ncols_pad) of `out` are zero-filled by the kernel
     g.cnt = cnt.data_ptr() if cnt is not None else None
-    if LINEAR_REPLAY is not None:
-        def reissue(ptr_of, g=g, a=a, out=out):     # ptr_of: tensor -> device pointer of the replaying stream's own copy
+
+    def issue(ptr_of=None):        # ptr_of: tensor -> device pointer of the replaying stream's own copy
+        g2 = g
+        if ptr_of is not None:
             g2 = L.LinearArgs.from_buffer_copy(g)
             g2.a, g2.y = ptr_of(a), ptr_of(out)
-            L.call("det6d_linear", ctypes.byref(g2), L.stream_ptr())
-        LINEAR_REPLAY.append((reissue, out, (g, a, w, shift, out, idx, ctr, cnt, compact)))
-    if LINEAR_EVENTS is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        L.call("det6d_linear", ctypes.byref(g), L.stream_ptr())
-        e1.record()
-        LINEAR_EVENTS.append((e0, e1, g.rows if compact is None else compact.hdr, g.k, g.ncols))
-        return out
-    L.call("det6d_linear", ctypes.byref(g), L.stream_ptr())
+        L.call("det6d_linear", ctypes.byref(g2), L.stream_ptr())
+    _launch(issue, (g.rows if compact is None else compact.hdr, g.k, g.ncols), (out, (g, a, w, shift, out, idx, ctr, cnt, compact)))
     return out
 
 
-def group_expand(p, pcol0, w, shift, act, c1, rows_pts, ctr, out, idx=None, compact=None):
+def layer(x, folded, out=None, **kw):
+    """one folded layer (W, shift, cout, act) through linear(); kw: its gathered (idx, ctr), compact (compact, gather) and
+    pooled (col0, cnt, pool) forms.  Without `out` the layer is a hidden one: it gets a buffer of W's padded width over the rows
+    of its row space, and the kernel writes the padding columns as zeros (they feed the next layer's zero weight rows)."""
+    w, shift, cout, act = folded
+    if out is None:
+        out = hidden_buffer(x, w, kw.get('idx'), kw.get('compact'))
+        kw['ncols_pad'] = w.shape[1] if w.shape[1] != cout else 0
+    return linear(x, w, shift, act, out, ncols=cout, **kw)
+
+
+def hidden_buffer(x, w, idx=None, compact=None):
+    """(rows, padded width of W) for a hidden layer over a compact list, the dense rows of idx (B, m, ns) or the rows of x"""
+    rows = compact.capacity if compact is not None else idx.numel() if idx is not None else x.numel() // x.shape[-1]
+    return torch.empty((rows, w.shape[1]), dtype=torch.float32, device=x.device)
+
+
+def run_chain(x, layers, out=None, col0=0, keep=False):
+    """plain GEMM chain [(W, shift, cout, act)] over rows, one launch per layer; the last layer writes into `out` at column
+    `col0` when given and stays hidden (padded width) otherwise.  -> the last activation, with keep the list of all of them"""
+    acts = []
+    for li, folded in enumerate(layers):
+        if li == len(layers) - 1 and out is not None:
+            x = layer(x, folded, out, col0=col0)
+        else:
+            x = layer(x, folded)
+        acts.append(x)
+    return acts if keep else x
+
+
+def rows_chain(layers, k0, out, wrow0=0, ocol0=0):
+    """det6d_mlp_rows chain spec [(w, wrow0, shift, k, n, act, out, ocol0)] of a folded chain: the first layer reads k0 input
+    columns through the weight rows from wrow0 on, the last one writes `out` at column ocol0 (see mlp_rows_eligible)"""
+    spec, last = [], len(layers) - 1
+    for li, (w, shift, cout, act) in enumerate(layers):
+        spec.append((w, wrow0, shift, k0, cout, act, out if li == last else None, ocol0 if li == last else 0))
+        k0, wrow0 = cout, 0
+    return spec
+
+
+def pooled_buffer(rows, width, device):
+    """(rows, round4(width)) target of an SA layer's max-pools: the groups write columns [0, width), the padding is zeroed"""
+    pooled = torch.empty((rows, round4(width)), dtype=torch.float32, device=device)
+    if pooled.shape[1] != width:
+        pooled[:, width:].zero_()
+    return pooled
+
+
+def group_expand(p, pcol0, w, shift, act, c1, rows_pts, ctr, out=None, idx=None, compact=None):
     """first layer of a grouped MLP from the per-point partial sums P (csrc/expand.hip): out[r, :c1] for every grouped row
-    (dense: idx (B, m, ns); compact: CompactRows), pad columns of `out` zero-filled"""
+    (dense: idx (B, m, ns); compact: CompactRows), pad columns of `out` (default: a hidden_buffer) zero-filled"""
+    out = hidden_buffer(rows_pts, w, idx, compact) if out is None else out
     L.require_cuda(p, w, shift, rows_pts, ctr, out, idx)
     if compact is not None:
         L.call("det6d_group_expand", compact.capacity, c1, L.ptr(p), p.shape[-1], pcol0, L.ptr(w), w.shape[1], L.ptr(shift), act,
@@ -318,16 +388,8 @@ def mlp_group3(p, pcol0, layers, rows_pts, ctr, out, col0, idx=None, cnt=None, c
         L.call("det6d_mlp_group3", rows, L.ptr(p), p.shape[-1], pcol0, L.ptr(w1), w1.shape[1], L.ptr(s1), c1, L.ptr(w2), w2.shape[1],
                L.ptr(s2), c2, L.ptr(w3), w3.shape[1], L.ptr(s3), c3, L.ptr(rows_pts), rows_pts.shape[-1], L.ptr(ctr), ctr.shape[-1],
                *tail, y, out.shape[-1], col0, L.stream_ptr())
-    ev = None
-    if LINEAR_EVENTS is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
-    if LINEAR_REPLAY is not None:
-        LINEAR_REPLAY.append((issue, out, (p, layers, rows_pts, ctr, out, idx, cnt, compact), [compact.hdr] if compact is not None else []))
-    issue()
-    if ev is not None:
-        ev[1].record()
-        LINEAR_EVENTS.append((ev[0], ev[1], hdr, 1, c1 * c2 + c2 * c3))
+    _launch(issue, (hdr, 1, c1 * c2 + c2 * c3),
+            (out, (p, layers, rows_pts, ctr, out, idx, cnt, compact), [compact.hdr] if compact is not None else []))
     return out
 
 
@@ -369,17 +431,8 @@ def mlp_rows(x, xcol0, chains):
         _, counts, arr = _rows_descriptors(chains, ptr_of)
         L.call("det6d_mlp_rows", rows, L.ptr(x) if ptr_of is None else ctypes.c_void_p(ptr_of(x)), x.shape[-1], xcol0, len(chains),
                counts, arr, L.stream_ptr())
-    ev = None
-    if LINEAR_EVENTS is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
-    if LINEAR_REPLAY is not None:
-        outs = [l[6] for l in flat if l[6] is not None]
-        LINEAR_REPLAY.append((issue, outs[-1], (x, chains)))
-    issue()
-    if ev is not None:
-        ev[1].record()
-        LINEAR_EVENTS.append((ev[0], ev[1], rows, 1, sum(l[3] * l[4] for l in flat)))
+    outs = [l[6] for l in flat if l[6] is not None]
+    _launch(issue, (rows, 1, sum(l[3] * l[4] for l in flat)), (outs[-1] if outs else None, (x, chains)))
 
 
 def sigmoid_pow(scores, gamma, out=None):
@@ -540,21 +593,13 @@ def mlp_chain3_compact(rows_pts, cr, ctr, layers, out, col0):
     """mlp_chain3 over a CompactRows list"""
     L.require_cuda(rows_pts, ctr, out)
     (w1, s1, c1, _), (w2, s2, c2, _), (w3, s3, c3, _) = layers
-    ev = None
-    if LINEAR_EVENTS is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
+
     def issue(ptr_of=None):
         y = L.ptr(out) if ptr_of is None else ctypes.c_void_p(ptr_of(out))
         L.call("det6d_mlp_chain3_compact", cr.capacity, L.ptr(cr.hdr), L.ptr(cr.crow_p), L.ptr(cr.crow_c), L.ptr(rows_pts),
                rows_pts.shape[-1], L.ptr(ctr), ctr.shape[-1], L.ptr(w1), w1.shape[1], L.ptr(s1), c1, L.ptr(w2), w2.shape[1],
                L.ptr(s2), c2, L.ptr(w3), w3.shape[1], L.ptr(s3), c3, y, out.shape[-1], col0, L.stream_ptr())
-    if LINEAR_REPLAY is not None:
-        LINEAR_REPLAY.append((issue, out, (rows_pts, cr, ctr, layers, out)))
-    issue()
-    if ev is not None:
-        ev[1].record()
-        LINEAR_EVENTS.append((ev[0], ev[1], cr.hdr, 1, (rows_pts.shape[-1] * c1 + c1 * c2 + c2 * c3)))
+    _launch(issue, (cr.hdr, 1, rows_pts.shape[-1] * c1 + c1 * c2 + c2 * c3), (out, (rows_pts, cr, ctr, layers, out)))
     return out
 
 
@@ -563,17 +608,13 @@ def mlp_chain3(rows_pts, idx, ctr, cnt, layers, out, col0):
     L.require_cuda(rows_pts, idx, ctr, cnt, out)
     b, m, ns = idx.shape
     (w1, s1, c1, _), (w2, s2, c2, _), (w3, s3, c3, _) = layers
-    ev = None
-    if LINEAR_EVENTS is not None:   # the chain is part of the MLP GEMM family bench.py prices
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
-    L.call("det6d_mlp_chain3", b * m * ns, rows_pts.shape[1], m, ns, L.ptr(rows_pts), rows_pts.shape[-1], L.ptr(idx),
-           L.ptr(ctr), ctr.shape[-1], L.ptr(cnt), L.ptr(w1), w1.shape[1], L.ptr(s1), c1, L.ptr(w2), w2.shape[1],
-           L.ptr(s2), c2, L.ptr(w3), w3.shape[1], L.ptr(s3), c3, L.ptr(out), out.shape[-1], col0, L.stream_ptr())
-    if ev is not None:
-        ev[1].record()
-        r = b * m * ns
-        LINEAR_EVENTS.append((ev[0], ev[1], r, 1, (rows_pts.shape[-1] * c1 + c1 * c2 + c2 * c3)))
+
+    def issue():
+        L.call("det6d_mlp_chain3", b * m * ns, rows_pts.shape[1], m, ns, L.ptr(rows_pts), rows_pts.shape[-1], L.ptr(idx),
+               L.ptr(ctr), ctr.shape[-1], L.ptr(cnt), L.ptr(w1), w1.shape[1], L.ptr(s1), c1, L.ptr(w2), w2.shape[1],
+               L.ptr(s2), c2, L.ptr(w3), w3.shape[1], L.ptr(s3), c3, L.ptr(out), out.shape[-1], col0, L.stream_ptr())
+    # part of the MLP GEMM family bench.py prices; the dense chain is not among the launches it replays
+    _launch(issue, (b * m * ns, 1, rows_pts.shape[-1] * c1 + c1 * c2 + c2 * c3))
     return out
 
 

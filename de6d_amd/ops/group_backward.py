@@ -34,10 +34,6 @@ def _i32(t, shape, what, who):
     return t
 
 
-def round4(v):
-    return (v + 3) // 4 * 4
-
-
 def group_gather(pts, idx, ctr, k=None, out=None):
     """pts (B, n, ldp) point rows [xyz | features | pad]; idx (B, M, ns) int32; ctr (B, M, >= 3) -> out (B * M * ns, ldout):
     columns [0, 3) = pts[idx] - ctr, [3, k) copied, [k, ldout) zero.  k defaults to ldp; out to a dense (rows, round4(k))."""
@@ -54,7 +50,7 @@ def group_gather(pts, idx, ctr, k=None, out=None):
     k = ldp if k is None else k
     rows = b * m * ns
     if out is None:
-        out = torch.empty((rows, round4(k)), dtype=torch.float32, device=pts.device)
+        out = torch.empty((rows, fused.round4(k)), dtype=torch.float32, device=pts.device)
     if _f32(out, 2, 'out', who).shape[0] != rows:
         raise L.Det6dError("%s: out has %d rows, %d expected" % (who, out.shape[0], rows))
     L.call_ext("det6d_ext_group_gather", b, n, m, ns, L.ptr(pts), ldp, k, L.ptr(idx), L.ptr(ctr), ctr.shape[2], L.ptr(out),
@@ -130,17 +126,8 @@ def group_forward(xyz_rows, idx, cnt, ctr, layers):
     if w0.shape[0] != xyz_rows.shape[-1]:
         raise L.Det6dError("group_forward: the first layer has %d weight rows, the point rows %d floats" % (w0.shape[0], xyz_rows.shape[-1]))
     x0 = group_gather(xyz_rows, idx, ctr, out=torch.empty((b * m * ns, w0.shape[0]), dtype=torch.float32, device=xyz_rows.device))
-    acts, x = [], None
-    for li, (w, shift, cout, act) in enumerate(layers):
-        y = torch.empty((b * m * ns, w.shape[1]), dtype=torch.float32, device=xyz_rows.device)
-        kw = dict(ncols=cout, ncols_pad=w.shape[1] if w.shape[1] != cout else 0)
-        if li == 0:
-            fused.linear(xyz_rows, w, shift, act, y, idx=idx, ctr=ctr, **kw)
-        else:
-            fused.linear(x, w, shift, act, y, **kw)
-        acts.append(y)
-        x = y
-    return x0, acts
+    first = fused.layer(xyz_rows, layers[0], idx=idx, ctr=ctr)
+    return x0, [first] + fused.run_chain(first, layers[1:], keep=True)
 
 
 class GroupedChain(torch.autograd.Function):
@@ -155,9 +142,7 @@ class GroupedChain(torch.autograd.Function):
         b, m = ctr.shape[0], ctr.shape[1]
         it = iter(tensors)
         groups = [[(next(it).detach(), next(it).detach(), c, a) for c, a in s] for s in group_specs]
-        pooled = torch.empty((b * m, round4(pooled_width)), dtype=torch.float32, device=ctr.device)
-        if pooled.shape[1] != pooled_width:
-            pooled[:, pooled_width:].zero_()
+        pooled = fused.pooled_buffer(b * m, pooled_width, ctr.device)
         saved, col = [], 0
         for (cnt, idx), layers in zip(found, groups):
             if layers[-1][3] != 1:

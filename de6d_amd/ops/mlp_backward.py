@@ -73,21 +73,12 @@ def linear_backward(x, w, dz, *, xcol0=0, wrow0=0, k=None, n=None, relu_input=Fa
 
 
 def chain_forward(x, layers, out=None, hidden_last=False):
-    """run_chain, keeping every layer's output: -> [activation of layer 0, ..., of the last layer].  Hidden activations are
-    (rows, padded width) with zeroed padding columns (the next layer's K), the last one is `out` or a dense (rows, cout) —
+    """fused.run_chain, keeping every layer's output: -> [activation of layer 0, ..., of the last layer].  Hidden activations
+    are (rows, padded width) with zeroed padding columns (the next layer's K), the last one is `out` or a dense (rows, cout) —
     unless hidden_last says that it feeds further layers too (a trunk under towers)."""
-    acts = []
-    rows = x.numel() // x.shape[-1]
-    for li, (w, shift, cout, act) in enumerate(layers):
-        if li == len(layers) - 1 and not hidden_last:
-            y = torch.empty((rows, cout), dtype=torch.float32, device=x.device) if out is None else out
-            fused.linear(x, w, shift, act, y, ncols=cout)
-        else:
-            y = torch.empty((rows, w.shape[1]), dtype=torch.float32, device=x.device)
-            fused.linear(x, w, shift, act, y, ncols=cout, ncols_pad=w.shape[1] if w.shape[1] != cout else 0)
-        acts.append(y)
-        x = y
-    return acts
+    if out is None and not hidden_last:
+        out = torch.empty((x.numel() // x.shape[-1], layers[-1][2]), dtype=torch.float32, device=x.device)
+    return fused.run_chain(x, layers, out=None if hidden_last else out, keep=True)
 
 
 def chain_backward(x, layers, activations, dz_last, *, k0=None, wrow0=0, relu_input=False, dx=None, accumulate_dx=False,

@@ -54,8 +54,8 @@ import torch
 import torch.nn as nn
 
 from ...ops.pointnet2.pointnet2_batch import pointnet2_modules
-from ...ops.pointnet2.pointnet2_batch.pointnet2_modules import fold_sequential, rows_ld, round4, run_chain, to_device
-from ...ops_backend import fused, pointnet2_batch_hip as pn2
+from ...ops.pointnet2.pointnet2_batch.pointnet2_modules import fold_sequential, neighbour_search, to_device
+from ...ops_backend import fused
 from ....ops import box_targets, group_backward, head_loss, mlp_backward
 from ...utils import box_coder_utils
 
@@ -120,10 +120,10 @@ class PointHeadBox6DVote(nn.Module):
             return self._folded
         if self.training:
             raise RuntimeError("the HIP head folds BatchNorm: call .eval() first")
-        ld = rows_ld(self.input_channels)
+        ld = fused.rows_ld(self.input_channels)
         sa_width = sum(seq[-3].out_channels for seq in self.SA_module.mlps)
-        shared = to_device(fold_sequential(self.shared_fc_layer, round4(sa_width)), device)
-        k = round4(shared[-1][2])
+        shared = to_device(fold_sequential(self.shared_fc_layer, fused.round4(sa_width)), device)
+        k = fused.round4(shared[-1][2])
         self._folded = dict(
             device=device,
             vote=to_device(fold_sequential(self.vote_layers, ld, k_offset=3), device),
@@ -144,7 +144,7 @@ class PointHeadBox6DVote(nn.Module):
             feats = batch_dict['point_features']
             n = coords.shape[0] // batch_size
             xyz = coords[:, 1:4].reshape(batch_size, n, 3).contiguous()
-            rows = torch.zeros((batch_size, n, rows_ld(feats.shape[-1])), dtype=torch.float32, device=feats.device)
+            rows = torch.zeros((batch_size, n, fused.rows_ld(feats.shape[-1])), dtype=torch.float32, device=feats.device)
             rows[:, :, :3] = xyz
             rows[:, :, 3:3 + feats.shape[-1]] = feats.reshape(batch_size, n, -1)
         f = self._prepare(rows.device)
@@ -154,40 +154,30 @@ class PointHeadBox6DVote(nn.Module):
         p = cand_rows.shape[1]
 
         # vote offsets -> clamp -> vote points (point_head_box6d_vote.py:815-821)
-        vote = f['vote']
-        spec, kin, wrow0 = [], self.input_channels, 3               # the chain starts at weight row 3 (rows 0..2: coordinates, zero)
-        off = torch.empty((b * p, round4(vote[-1][2])), dtype=torch.float32, device=rows.device)
-        for li, (w, sh, cout, act) in enumerate(vote):
-            spec.append((w, wrow0, sh, kin, cout, act, off if li == len(vote) - 1 else None, 0))
-            kin, wrow0 = cout, 0
+        off = torch.empty((b * p, fused.round4(f['vote'][-1][2])), dtype=torch.float32, device=rows.device)
+        # the chain starts at weight row 3 (rows 0..2: coordinates, zero)
+        spec = fused.rows_chain(f['vote'], self.input_channels, off, wrow0=3)
         if fused.mlp_rows_eligible(self.input_channels, [spec]):    # vote FC stack in one launch (csrc/mlp_rows.hip)
             fused.mlp_rows(cand_rows.view(b * p, ld), 3, [spec])
         else:
-            off = run_chain(cand_rows, f['vote'])                   # (B*P, 4), cols 0..2 valid
+            off = fused.run_chain(cand_rows, f['vote'])                   # (B*P, 4), cols 0..2 valid
         vote_xyz = torch.empty((b, p, 3), dtype=torch.float32, device=rows.device)
         off_clamped = torch.empty((b * p, 3), dtype=torch.float32, device=rows.device)
         fused.vote_points(off, cand_rows, self.vote_cfg.MAX_TRANSLATION_RANGE, vote_xyz, off_clamped)
 
         # SA layer around the votes, then the FC towers
         _, pooled, _ = self.SA_module.forward_rows(xyz, rows, new_xyz=vote_xyz)
-        shared = run_chain(pooled.view(b * p, -1), f['shared'])
+        shared = fused.run_chain(pooled.view(b * p, -1), f['shared'])
         ncls, ncode = f['cls'][-1][2], f['reg'][-1][2]
         point_cls_preds = torch.empty((b * p, ncls), dtype=torch.float32, device=rows.device)
         kshared = f['shared'][-1][2]
-
-        def tower(layers, out):
-            spec, kin = [], kshared
-            for li, (w, sh, cout, act) in enumerate(layers):
-                spec.append((w, 0, sh, kin, cout, act, out if li == len(layers) - 1 else None, 0))
-                kin = cout
-            return spec
         point_reg_preds = torch.empty((b * p, ncode), dtype=torch.float32, device=rows.device)
-        towers = [tower(f['cls'], point_cls_preds), tower(f['reg'], point_reg_preds)]
+        towers = [fused.rows_chain(f['cls'], kshared, point_cls_preds), fused.rows_chain(f['reg'], kshared, point_reg_preds)]
         if shared.shape[1] == kshared and fused.mlp_rows_eligible(kshared, towers):
             fused.mlp_rows(shared, 0, towers)                       # cls and reg towers: two chains, one launch (csrc/mlp_rows.hip)
         else:
-            run_chain(shared, f['cls'], out=point_cls_preds)        # the last layer writes the unpadded (B*P, ncls) logits
-            reg = run_chain(shared, f['reg'])
+            fused.run_chain(shared, f['cls'], out=point_cls_preds)        # the last layer writes the unpadded (B*P, ncls) logits
+            reg = fused.run_chain(shared, f['reg'])
             point_reg_preds = reg[:, :ncode].contiguous() if reg.shape[1] != ncode else reg
 
         vote_flat = vote_xyz.view(b * p, 3)
@@ -431,17 +421,7 @@ class PointHeadBox6DVote(nn.Module):
         off, = mlp_backward.folded_chain(cand_rows.view(b * p, ld), vote_chain)
         vote = group_backward.VotePoints.apply(off, cand_rows, tuple(self.vote_cfg.MAX_TRANSLATION_RANGE))
         centres = vote.detach()
-        shells = [(0.0, radius, nsample) for radius, nsample in zip(sa.radii, sa.nsamples)]
-        if len(shells) == 2:
-            ca, ia, cb, ib = fused.ball_query_pair(xyz, centres, shells[0], shells[1])
-            found = [(ca, ia), (cb, ib)]
-        else:
-            found, n = [], xyz.shape[1]
-            for _, radius, nsample in shells:
-                cnt = torch.zeros((b, p), dtype=torch.int32, device=xyz.device)
-                idx = torch.zeros((b, p, nsample), dtype=torch.int32, device=xyz.device)
-                pn2.ball_query_cnt_wrapper(b, n, p, radius, nsample, centres, xyz, cnt, idx)
-                found.append((cnt, idx))
+        found, _ = neighbour_search(xyz, centres, sa._shells(), False, want_lists=False)       # dense padded lists
         groups = [mlp_backward.folded_params(seq, layers) for seq, layers in zip(sa.mlps, f_sa['groups'])]
         pooled = group_backward.grouped_chain(rows, vote, found, groups, f_sa['pooled_width'])
         return vote, pooled.view(b, p, -1)

@@ -25,14 +25,7 @@ import torch.nn as nn
 from ....ops_backend import ffps, fused, pointnet2_batch_hip as pn2, sort_samplers
 from . import pointnet2_utils
 
-
-def round4(v):
-    return (v + 3) // 4 * 4
-
-
-def rows_ld(channels):
-    """row stride of a rows tensor carrying `channels` feature channels"""
-    return round4(3 + channels)
+round4, rows_ld, run_chain = fused.round4, fused.rows_ld, fused.run_chain     # (their importers find them here too)
 
 
 def _np(t):
@@ -84,20 +77,6 @@ def to_device(layers, device):
     return [(torch.from_numpy(m).to(device), torch.from_numpy(s).to(device), c, a) for m, s, c, a in layers]
 
 
-def run_chain(x, layers, out=None, col0=0):
-    """plain GEMM chain over rows; the last layer may write into `out` at column `col0`"""
-    for li, (w, shift, cout, act) in enumerate(layers):
-        last = li == len(layers) - 1
-        if last and out is not None:
-            fused.linear(x, w, shift, act, out, ncols=cout, col0=col0)
-            return out
-        y = torch.empty((x.numel() // x.shape[-1], w.shape[1]), dtype=torch.float32, device=x.device)
-        # padded columns feed the next layer's zero weight rows: the kernel writes them as zeros
-        fused.linear(x, w, shift, act, y, ncols=cout, ncols_pad=w.shape[1] if w.shape[1] != cout else 0)
-        x = y
-    return x
-
-
 #: The samplers of a layer run one after the other on the caller's stream.  Forking them onto side streams
 #: (DET6D_FORKED_SAMPLERS=1) shortens one pass by ~0.45 ms but costs throughput with many passes in flight
 #: (4121 vs 4300 scenes/s at 15 passes: more sampler workgroups resident at once, fork/join in every graph).
@@ -113,6 +92,90 @@ COMPACT_ROWS = os.environ.get('DET6D_DENSE_ROWS') is None
 #: layer + 3 FMAs per grouped output instead of a (3 + C)-deep GEMM over every (centre, neighbour) row; identical bits
 #: (the chain order of gathered rows puts the relative coordinates last).  DET6D_NO_EXPAND=1: the gathered GEMM instead.
 EXPAND_FIRST_LAYER = fused.L.experiment_switch('DET6D_NO_EXPAND') is None
+
+
+def compact_rows(nsample):
+    """does a radius group of this nsample run on a compact row list?"""
+    return COMPACT_ROWS and nsample in (4, 8, 16, 32)
+
+
+def group_route(lda, layers, nsample, compact, expand, b=0, m=0):
+    """Which launches evaluate a radius group: the name of one of six routes.
+
+      compact_chain / dense_chain    the whole group in one chain kernel (fused.mlp_chain3_compact / mlp_chain3)
+      compact_group / dense_group    first layer from the per-point partial sums, in one group kernel (fused.mlp_group3)
+      compact_layers / dense_layers  one launch per layer (group_layers)
+
+    lda: row stride of the point rows; layers: the group's folded chain; compact: compact_rows(nsample); expand: the group
+    is in the layer's expand set (its partial sums exist); b, m: scenes and centres per scene.  The library decides what its
+    kernels take (fused.chain_compact_eligible, chain_eligible, group_kernel_eligible); compact lists are not asked about
+    (b, m).  b = m = 0 asks by the widths alone: that is _prepare's question, which has to settle the expand set before m is
+    known.  The consequence: a group chained by its widths is not in the expand set, so where the library refuses its chain
+    at this (b, m) — odd m with nsample 16, b * m * nsample off the 32-row tiles — it cannot take the group kernel either
+    and runs per layer, its first layer the gathered det6d_linear."""
+    if compact:
+        if fused.chain_compact_eligible(lda, layers):
+            return 'compact_chain'
+        return 'compact_group' if expand and fused.group_kernel_eligible(layers, nsample, True) else 'compact_layers'
+    if fused.chain_eligible(lda, layers, nsample, b, m):
+        return 'dense_chain'
+    return 'dense_group' if expand and fused.group_kernel_eligible(layers, nsample, False, b, m) else 'dense_layers'
+
+
+def neighbour_search(xyz, centres, shells, dilated, want_lists):
+    """The ball queries of a layer: shells = [(radius_in, radius_out, nsample)] -> (found = [(cnt (B, m), idx (B, m, ns))]
+    per shell, counted).  Two shells go in one launch; with want_lists through the query that also counts the parts of the
+    compact lists where the shape qualifies (fused.ball_query_pair_lists): counted are then the two CompactRows for
+    fused.compact_groups_pair to place, otherwise None.  Any other number of shells: one query each."""
+    if len(shells) == 2:
+        fast = fused.ball_query_pair_lists(xyz, centres, shells[0], shells[1]) if want_lists else None
+        if fast is not None:
+            return [fast[0:2], fast[2:4]], fast[4:]
+        ca, ia, cb, ib = fused.ball_query_pair(xyz, centres, shells[0], shells[1])
+        return [(ca, ia), (cb, ib)], None
+    (b, n, _), m, found = xyz.shape, centres.shape[1], []
+    for rin, rout, nsample in shells:
+        idx_cnt = torch.zeros((b, m), dtype=torch.int32, device=xyz.device)
+        idx = torch.zeros((b, m, nsample), dtype=torch.int32, device=xyz.device)
+        if dilated:
+            pn2.ball_query_dilated_wrapper(b, n, m, rin, rout, nsample, centres, xyz, idx_cnt, idx)
+        else:
+            pn2.ball_query_cnt_wrapper(b, n, m, rout, nsample, centres, xyz, idx_cnt, idx)
+        found.append((idx_cnt, idx))
+    return found, None
+
+
+def single_list(idx_cnt, idx, n, pooled, col, width):
+    """the compact list of one group that the pair builder did not make.  Parts of a centre are combined by an atomic max, so
+    the group's slice of `pooled` is cleared first: by the builder itself where the columns allow, by a fill before it else"""
+    if fused.COMPACT_SPLIT and (col | width | pooled.shape[1]) % 4 == 0:
+        return fused.compact_groups(idx_cnt, idx, n, zero=(pooled, col, width))
+    if fused.COMPACT_SPLIT:
+        pooled[:, col:col + width].zero_()
+    return fused.compact_groups(idx_cnt, idx, n)
+
+
+def group_layers(rows, ctr, space, idx_cnt, layers, pooled, col, partial=None):
+    """A radius group with one launch per layer.  space: the group's row space, the dense idx (B, m, ns) or a CompactRows;
+    partial = (P, first column): the first layer from the per-point partial sums (fused.group_expand) instead of the gathered
+    GEMM.  The last layer pools into pooled[:, col:] in its epilogue (compact lists by class; dense rows for nsample 8, 16,
+    32); for any other nsample it is written out, and mask + max run in their own launch."""
+    compact = isinstance(space, fused.CompactRows)
+    where = dict(compact=space) if compact else dict(idx=space)
+    nsample = space.ns if compact else space.shape[2]
+    pool = -1 if compact else nsample if nsample in (8, 16, 32) else 0
+    first, later = dict(where, ctr=ctr, gather=compact), (where if compact else {})     # the gathered layer, the plain ones
+    x = None
+    for li, folded in enumerate(layers):
+        kw = first if li == 0 else later
+        if li == len(layers) - 1 and pool:
+            return fused.layer(rows if li == 0 else x, folded, pooled, col0=col, cnt=idx_cnt, pool=pool, **kw)
+        if li == 0 and partial is not None:
+            w, shift, cout, act = folded
+            x = fused.group_expand(partial[0], partial[1], w, shift, act, cout, rows, ctr, **where)
+        else:
+            x = fused.layer(rows if li == 0 else x, folded, **kw)
+    fused.group_maxpool(x, nsample, layers[-1][2], idx_cnt, pooled, col)
 
 
 class _PointnetSAModuleFSBase(nn.Module):
@@ -155,10 +218,7 @@ class _PointnetSAModuleFSBase(nn.Module):
         # groups whose first layer runs as "per-point GEMM + expand" (not the ones a fused chain kernel takes whole)
         expand, pcols, col = [], {}, 0
         for gi, (layers, ns) in enumerate(zip(groups, self.nsamples)):
-            if COMPACT_ROWS and ns in (4, 8, 16, 32):
-                chained = fused.chain_compact_eligible(in_ld, layers)
-            else:
-                chained = fused.chain_eligible(in_ld, layers, ns)
+            chained = group_route(in_ld, layers, ns, compact_rows(ns), False).endswith('_chain')      # by its widths
             if EXPAND_FIRST_LAYER and not chained and len(layers) >= 2 and layers[0][2] % 4 == 0 and in_ld > 4:
                 expand.append(gi)
                 pcols[gi] = col
@@ -249,154 +309,84 @@ class _PointnetSAModuleFSBase(nn.Module):
         if self.pool_method != 'max_pool' or self.skip_connection:
             raise NotImplementedError("only max_pool without skip connection is on the Det6D path")
         f = self._prepare(rows.device)
-        b, n, _ = xyz.shape
-        new_rows = None
-        if new_xyz is None:
-            sample_idx = self._sample(xyz, scores, rows)
-            m = sample_idx.shape[1]
-            if f['agg'] is not None:  # next level's rows: xyz now, features by the aggregation GEMM, pad zeroed
-                ld_next = rows_ld(f['out_channels'])
-                new_rows = torch.empty((b, m, ld_next), dtype=torch.float32, device=rows.device)
-                new_xyz = fused.gather_centres(xyz, sample_idx, new_rows, 3 + f['out_channels'])
-            else:
-                new_xyz = fused.gather_centres(xyz, sample_idx)
+        b, n, lda = rows.shape
+        new_xyz, new_rows = self._centres(f, xyz, rows, scores, new_xyz)
         m = new_xyz.shape[1]
-        pooled = torch.empty((b * m, round4(f['pooled_width'])), dtype=torch.float32, device=rows.device)
-        if pooled.shape[1] != f['pooled_width']:
-            pooled[:, f['pooled_width']:].zero_()
-        col = 0
-        # neighbour search: shells [former, radius) when dilated, plain balls otherwise
-        shells, former_radius = [], 0.0
-        for radius, nsample in zip(self.radii, self.nsamples):
-            shells.append((former_radius if self.dilated_radius_group else 0.0, radius, nsample))
-            former_radius = radius
-        counted = None
+        pooled = fused.pooled_buffer(b * m, f['pooled_width'], rows.device)
         widths = [layers[-1][2] for layers in f['groups']]
-        if len(shells) == 2:
-            fast = None
-            if COMPACT_ROWS and (widths[0] | widths[1] | pooled.shape[1]) % 4 == 0:
-                # compact-row engine on a large cloud: the query counts the list builder's parts and skips the padding slots
-                fast = fused.ball_query_pair_lists(xyz, new_xyz, shells[0], shells[1])
-            if fast is not None:
-                ca, ia, cb, ib = fast[:4]
-                counted = fast[4:]
-            else:
-                ca, ia, cb, ib = fused.ball_query_pair(xyz, new_xyz, shells[0], shells[1])
-            found = [(ca, ia), (cb, ib)]
-        else:
-            found = []
-            for rin, rout, nsample in shells:
-                idx_cnt = torch.zeros((b, m), dtype=torch.int32, device=xyz.device)
-                idx = torch.zeros((b, m, nsample), dtype=torch.int32, device=xyz.device)
-                if self.dilated_radius_group:
-                    pn2.ball_query_dilated_wrapper(b, n, m, rin, rout, nsample, new_xyz, xyz, idx_cnt, idx)
-                else:
-                    pn2.ball_query_cnt_wrapper(b, n, m, rout, nsample, new_xyz, xyz, idx_cnt, idx)
-                found.append((idx_cnt, idx))
+        # both lists of a two-group layer come from one builder when every column offset is a multiple of 4
+        paired = COMPACT_ROWS and len(widths) == 2 and (widths[0] | widths[1] | pooled.shape[1]) % 4 == 0
+        found, counted = neighbour_search(xyz, new_xyz, self._shells(), self.dilated_radius_group, want_lists=paired)
         lists = [None] * len(found)
-        if (COMPACT_ROWS and fused.COMPACT_SPLIT and len(found) == 2 and all(ns in (4, 8, 16, 32) for ns in self.nsamples)
-                and (widths[0] | widths[1] | pooled.shape[1]) % 4 == 0):
-            # both groups' lists in one pair of launches; their slices of `pooled` are cleared by the builder
+        if paired and fused.COMPACT_SPLIT and all(ns in (4, 8, 16, 32) for ns in self.nsamples):
+            # (their slices of `pooled` are cleared by the builder)
             lists = fused.compact_groups_pair(found, n, pooled, [(0, widths[0]), (widths[0], widths[1])], counted=counted)
         p_all = None
         if f['expand']:   # per-point partial sums of the first layers of all expand groups: one plain GEMM over the points
             p_all = torch.empty((b * n, f['p_w'].shape[1]), dtype=torch.float32, device=rows.device)
-            fused.linear(rows.view(b * n, rows.shape[-1]), f['p_w'], None, 0, p_all)
+            fused.linear(rows.view(b * n, lda), f['p_w'], None, 0, p_all)
+        col = 0
         for gi, ((idx_cnt, idx), nsample, layers, cr) in enumerate(zip(found, self.nsamples, f['groups'], lists)):
-            if COMPACT_ROWS and nsample in (4, 8, 16, 32):
-                # parts of a centre are combined by an atomic max: the group's slice of `pooled` is cleared by the list builder
-                w_out = layers[-1][2]
-                if cr is not None:
-                    pass
-                elif fused.COMPACT_SPLIT and (col | w_out | pooled.shape[1]) % 4 == 0:
-                    cr = fused.compact_groups(idx_cnt, idx, n, zero=(pooled, col, w_out))
-                else:
-                    if fused.COMPACT_SPLIT:
-                        pooled[:, col:col + w_out].zero_()
-                    cr = fused.compact_groups(idx_cnt, idx, n)
-                if fused.chain_compact_eligible(rows.shape[-1], layers):
-                    fused.mlp_chain3_compact(rows, cr, new_xyz, layers, pooled, col)
-                    col += layers[-1][2]
-                    continue
-                if gi in f['expand'] and fused.group_kernel_eligible(layers, nsample, True):
-                    fused.mlp_group3(p_all, f['pcols'][gi], layers, rows, new_xyz, pooled, col, compact=cr)
-                    col += layers[-1][2]
-                    continue
-                x = None
-                for li, (w, shift, cout, act) in enumerate(layers):
-                    if li == len(layers) - 1:
-                        tgt, kw = pooled, dict(ncols=cout, col0=col, cnt=idx_cnt, pool=-1)
-                    else:
-                        tgt = torch.empty((cr.capacity, w.shape[1]), dtype=torch.float32, device=rows.device)
-                        kw = dict(ncols=cout, ncols_pad=w.shape[1] if w.shape[1] != cout else 0)
-                    if li == 0 and gi in f['expand']:
-                        fused.group_expand(p_all, f['pcols'][gi], w, shift, act, cout, rows, new_xyz, tgt, compact=cr)
-                    elif li == 0:
-                        fused.linear(rows, w, shift, act, tgt, ctr=new_xyz, compact=cr, gather=True, **kw)
-                    else:
-                        fused.linear(x, w, shift, act, tgt, compact=cr, **kw)
-                    x = tgt
-                col += layers[-1][2]
-                continue
-            if fused.chain_eligible(rows.shape[-1], layers, nsample, b, m):   # narrow group: one fused launch
+            compact, expand = compact_rows(nsample), gi in f['expand']
+            route = group_route(lda, layers, nsample, compact, expand, b, m)
+            if compact and cr is None:
+                cr = single_list(idx_cnt, idx, n, pooled, col, widths[gi])
+            if route == 'compact_chain':
+                fused.mlp_chain3_compact(rows, cr, new_xyz, layers, pooled, col)
+            elif route == 'dense_chain':
                 fused.mlp_chain3(rows, idx, new_xyz, idx_cnt, layers, pooled, col)
-                col += layers[-1][2]
-                continue
-            if gi in f['expand'] and fused.group_kernel_eligible(layers, nsample, False, b, m):
+            elif route == 'compact_group':
+                fused.mlp_group3(p_all, f['pcols'][gi], layers, rows, new_xyz, pooled, col, compact=cr)
+            elif route == 'dense_group':
                 fused.mlp_group3(p_all, f['pcols'][gi], layers, rows, new_xyz, pooled, col, idx=idx, cnt=idx_cnt)
-                col += layers[-1][2]
-                continue
-            # one launch per layer.  Also the route of a group that _prepare counted as chained (by its widths) and that the
-            # library refuses at this (b, m) — odd m with nsample 16, b * m * nsample off the 32-row tiles: such a group is
-            # not in f['expand'], so its first layer is the gathered det6d_linear below
-            x = None
-            for li, (w, shift, cout, act) in enumerate(layers):
-                last = li == len(layers) - 1
-                poolable = nsample in (8, 16, 32)
-                if last and poolable:
-                    tgt, kw = pooled, dict(ncols=cout, col0=col, cnt=idx_cnt, pool=nsample)
-                else:
-                    tgt = torch.empty((b * m * nsample, w.shape[1]), dtype=torch.float32, device=rows.device)
-                    kw = dict(ncols=cout, ncols_pad=w.shape[1] if w.shape[1] != cout else 0)
-                if li == 0 and gi in f['expand'] and not last:
-                    fused.group_expand(p_all, f['pcols'][gi], w, shift, act, cout, rows, new_xyz, tgt, idx=idx)
-                elif li == 0:
-                    fused.linear(rows, w, shift, act, tgt, idx=idx, ctr=new_xyz, **kw)
-                else:
-                    fused.linear(x, w, shift, act, tgt, **kw)
-                x = tgt
-                if last and not poolable:  # any other nsample: the layer is written out, mask + max in their own launch
-                    fused.group_maxpool(x, nsample, cout, idx_cnt, pooled, col)
-            col += layers[-1][2]
-        new_scores = None
-        if f['agg'] is not None:
-            if new_rows is None:  # centres supplied by the caller
-                new_rows = torch.zeros((b, m, rows_ld(f['out_channels'])), dtype=torch.float32, device=rows.device)
-                new_rows[:, :, :3] = new_xyz
-            if f['conf'] is not None and f['conf'][-1][2] == 1 and len(f['agg']) == 1:
-                # aggregation + confidence chain in ONE launch (csrc/mlp_rows.hip): the aggregated features go to the next
-                # level's rows AND stay in LDS as the input of the confidence layers (whose first three weight rows, the
-                # coordinates', are zero: the chain starts at weight row 3)
-                wa, sha, ca, aa = f['agg'][0]
-                new_scores = torch.empty((b * m, 1), dtype=torch.float32, device=rows.device)
-                spec = [(wa, 0, sha, f['pooled_width'], ca, aa, new_rows.view(b * m, -1), 3)]
-                kin, wrow0 = ca, 3
-                for li, (w, sh, cout, act) in enumerate(f['conf']):
-                    spec.append((w, wrow0, sh, kin, cout, act, new_scores if li == len(f['conf']) - 1 else None, 0))
-                    kin, wrow0 = cout, 0
-                if fused.mlp_rows_eligible(f['pooled_width'], [spec]):
-                    fused.mlp_rows(pooled, 0, [spec])
-                    return new_xyz, new_rows, new_scores.view(b, m)
-                new_scores = None
-            run_chain(pooled, f['agg'], out=new_rows, col0=3)
-            if f['conf'] is not None and f['conf'][-1][2] == 1:   # the last layer writes the (B*M, 1) score column itself
-                new_scores = torch.empty((b * m, 1), dtype=torch.float32, device=rows.device)
-                run_chain(new_rows, f['conf'], out=new_scores)
-                new_scores = new_scores.view(b, m)
-            elif f['conf'] is not None:
-                new_scores = run_chain(new_rows, f['conf'])[:, 0].reshape(b, m).contiguous()
-            return new_xyz, new_rows, new_scores
-        return new_xyz, pooled.view(b, m, -1), None
+            else:
+                group_layers(rows, new_xyz, cr if compact else idx, idx_cnt, layers, pooled, col,
+                             partial=(p_all, f['pcols'][gi]) if expand else None)
+            col += widths[gi]
+        if f['agg'] is None:
+            return new_xyz, pooled.view(b, m, -1), None
+        if new_rows is None:  # centres supplied by the caller
+            new_rows = torch.zeros((b, m, rows_ld(f['out_channels'])), dtype=torch.float32, device=rows.device)
+            new_rows[:, :, :3] = new_xyz
+        return new_xyz, new_rows, self._aggregate(f, pooled, new_rows)
+
+    def _shells(self):
+        """[(radius_in, radius_out, nsample)] of the groups: shells [former radius, radius) when dilated, else plain balls"""
+        inner = [0.0] + list(self.radii[:-1]) if self.dilated_radius_group else [0.0] * len(self.radii)
+        return list(zip(inner, self.radii, self.nsamples))
+
+    def _centres(self, f, xyz, rows, scores, new_xyz):
+        """sample (unless the caller supplies the centres) -> (new_xyz, next level's rows with the centres in or None)"""
+        if new_xyz is not None:
+            return new_xyz, None
+        sample_idx = self._sample(xyz, scores, rows)
+        if f['agg'] is None:
+            return fused.gather_centres(xyz, sample_idx), None
+        # next level's rows: xyz now, features by the aggregation GEMM, pad zeroed
+        new_rows = torch.empty((xyz.shape[0], sample_idx.shape[1], rows_ld(f['out_channels'])), dtype=torch.float32, device=rows.device)
+        return fused.gather_centres(xyz, sample_idx, new_rows, 3 + f['out_channels']), new_rows
+
+    def _aggregate(self, f, pooled, new_rows):
+        """aggregation MLP: pooled -> the feature columns of new_rows; confidence MLP on top of them -> scores (B, M) or None"""
+        b, m, _ = new_rows.shape
+        rows2d = new_rows.view(b * m, -1)
+        conf = f['conf']
+        scores = torch.empty((b * m, 1), dtype=torch.float32, device=pooled.device) if conf is not None and conf[-1][2] == 1 else None
+        if scores is not None and len(f['agg']) == 1:
+            # aggregation + confidence chain in ONE launch (csrc/mlp_rows.hip): the aggregated features go to the next
+            # level's rows AND stay in LDS as the input of the confidence layers (whose first three weight rows, the
+            # coordinates', are zero: the chain starts at weight row 3)
+            spec = (fused.rows_chain(f['agg'], f['pooled_width'], rows2d, ocol0=3)
+                    + fused.rows_chain(conf, f['agg'][0][2], scores, wrow0=3))
+            if fused.mlp_rows_eligible(f['pooled_width'], [spec]):
+                fused.mlp_rows(pooled, 0, [spec])
+                return scores.view(b, m)
+        run_chain(pooled, f['agg'], out=new_rows, col0=3)
+        if conf is None:
+            return None
+        if scores is not None:   # the last layer writes the (B*M, 1) score column itself
+            return run_chain(new_rows, conf, out=scores).view(b, m)
+        return run_chain(new_rows, conf)[:, 0].reshape(b, m).contiguous()
 
     # ---- reference-shaped signature -----------------------------------------------------
     def forward(self, xyz, features=None, new_xyz=None, scores=None):

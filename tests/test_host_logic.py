@@ -508,6 +508,37 @@ def test_fused_predicates_ask_the_plan():
     assert not fused.group_kernel_eligible(layers(128, 128, 128), 16, False) and not fused.group_kernel_eligible(group, 8, False)
 
 
+def test_group_route_names_one_of_six_routes():
+    """pointnet2_modules.group_route at the shapes of the configs: kitti det6d_car's SA1 (point rows of 4 floats), SA2 (68),
+    SA3 (132) and head (260), det6d_tiny's SA1 (4) and SA2 (20); and the refusals of tests/gpu_scripts/sa_odd_centres.py: a
+    wide chain on dense rows, chained by its widths, refused at three centres, taken at four"""
+    from de6d_amd.pcdet.ops.pointnet2.pointnet2_batch.pointnet2_modules import group_route
+    layers = lambda *c: [(None, None, n, 1) for n in c]   # noqa: E731
+    # (lda, layers, nsample, compact rows, in the expand set, b, m)
+    assert group_route(4, layers(16, 16, 32), 16, True, False, 2, 4096) == 'compact_chain'
+    assert group_route(4, layers(32, 32, 64), 32, True, False, 2, 4096) == 'compact_chain'
+    assert group_route(68, layers(64, 96, 128), 32, True, False, 2, 1024) == 'compact_chain'
+    assert group_route(132, layers(128, 128, 256), 16, True, True, 2, 512) == 'compact_group'
+    assert group_route(260, layers(256, 512, 1024), 32, True, True, 2, 256) == 'compact_group'
+    assert group_route(132, layers(128, 128, 256), 16, True, False, 2, 512) == 'compact_layers'     # no partial sums: no group kernel
+    assert group_route(4, layers(8, 8, 16), 16, True, False, 3, 512) == 'compact_layers'            # widths without a register chain
+    assert group_route(20, layers(16, 16, 32), 16, True, True, 3, 256) == 'compact_layers'
+    assert group_route(4, layers(8), 4, True, False, 2, 64) == 'compact_layers'                     # a single layer
+    assert group_route(4, layers(16, 16, 32), 16, False, False, 2, 4096) == 'dense_chain'
+    assert group_route(4, layers(8, 8, 16), 32, False, False, 3, 512) == 'dense_chain'              # the LDS chain takes any narrow widths
+    assert group_route(68, layers(64, 64, 128), 16, False, False, 2, 1024) == 'dense_chain'
+    assert group_route(132, layers(128, 256, 256), 32, False, True, 2, 512) == 'dense_group'
+    assert group_route(260, layers(256, 256, 512), 16, False, True, 2, 256) == 'dense_group'
+    assert group_route(132, layers(128, 256, 256), 32, False, False, 2, 512) == 'dense_layers'
+    assert group_route(20, layers(16, 16, 32), 16, False, True, 3, 256) == 'dense_layers'
+    assert group_route(8, layers(16, 16, 32), 12, False, True, 2, 63) == 'dense_layers'             # nsample off the tiles
+    assert group_route(260, layers(256, 256, 512), 16, False, True, 1, 3) == 'dense_layers'         # odd m with nsample 16
+    for wide in (layers(64, 64, 128), layers(64, 96, 128)):
+        assert group_route(68, wide, 16, False, False) == 'dense_chain'                             # _prepare's question: b = m = 0
+        assert group_route(68, wide, 16, False, False, 1, 3) == 'dense_layers'
+        assert group_route(68, wide, 16, False, False, 1, 4) == 'dense_chain'
+
+
 def test_bench_refuses_more_ranks_than_devices():
     """`bench.py --gpus N` with fewer than N visible devices exits non-zero BEFORE any rank is started or any rendezvous is
     attempted (a rank that left alone would keep the others waiting for the store's ten-minute time-out); decided from

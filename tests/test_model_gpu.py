@@ -61,6 +61,38 @@ def test_tiny_model_bit_exact(oracle_ops, seed, tilt):
     assert sum(len(p['pred_scores']) for p in pred) > 0
 
 
+def test_tiny_pass_launches_what_the_stubbed_trace_says(oracle_ops):
+    """tests/launch_trace.py listening to a real eager pass: the same entries as the stubbed recording of this process, so the
+    stubs of tests/test_launch_trace.py change no route, and as the trace recorded without a GPU (tests/traces/: the default
+    routes, or the dense rows tests/test_compact_gpu.py reruns this file on; its other switches have no fixture of this
+    case); and listening changes no result: the pass still equals the oracle's"""
+    import json
+    import os
+    from de6d_amd.runtime import load_config, build_model
+    from oracle import model as omodel
+    from tests import launch_trace
+    cfg = load_config('synthetic_models/det6d_tiny.yaml')
+    model = build_model(cfg, seed=11, device='cuda')
+    pts = flat_points(make_batch(11, 3, 2048))
+    with launch_trace.record(passthrough=True) as trace:
+        bd = launch_trace.run_modules(model, 3, 2048, points=torch.from_numpy(pts).cuda())
+    with torch.no_grad():
+        pred, _ = model.post_processing(bd)
+    got = json.loads(json.dumps(trace))
+    switches = sorted(k for k in os.environ if k.startswith('DET6D_') and k != 'DET6D_EXPERIMENTS_LIB')
+    recorded = {(): 'tiny_b3_n2048', ('DET6D_DENSE_ROWS',): 'tiny_b3_n2048_dense_rows'}.get(tuple(switches))
+    wants = [json.loads(json.dumps(launch_trace.CASES['tiny_b3_n2048'][0]()))]
+    if recorded is not None:
+        wants.append(launch_trace.fixture(recorded))
+    for want in wants:
+        assert [e[0] for e in got] == [e[0] for e in want]
+        for i, (g, w) in enumerate(zip(got, want)):
+            assert g == w, "launch %d" % i
+    sd = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
+    check(bd, pred, omodel.forward(cfg.MODEL, sd, pts, 3), 3)
+    assert sum(len(p['pred_scores']) for p in pred) > 0
+
+
 def test_full_car_model_bit_exact(oracle_ops):
     """BASELINE config 2 shapes (16384-point scenes, full-width network), 2 scenes"""
     cfg, bd, pred, ref = run_both('kitti_models/det6d_car.yaml', 2, 16384, 21)

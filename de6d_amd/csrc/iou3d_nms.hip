@@ -134,11 +134,8 @@ int run_nms(int boxes_num, const float *boxes, float thresh, uint64_t *mask, int
   if (chunk_rows < 1) chunk_rows = 1;
   const size_t greedy_lds = ((size_t)col_blocks + (size_t)chunk_rows * col_blocks) * sizeof(unsigned long long);
   if (greedy_lds > 128 * 1024) return DET6D_EINVAL;   // > ~390 k boxes
-  static bool greedy_attr = false;
-  if (!greedy_attr) {
-    hipFuncSetAttribute((const void *)nms_greedy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    greedy_attr = true;
-  }
+  // above the 64 KB default from K = 705; a limit the device refuses shows as the launch's error below
+  DET6D_MAX_DYNAMIC_LDS(nms_greedy_kernel, 128 * 1024);
   hipLaunchKernelGGL(nms_greedy_kernel, dim3(1), dim3(64), greedy_lds, stream, boxes_num, chunk_rows,
                      (const unsigned long long *)mask, (long long *)keep, num_keep);
   return det6d_check_launch("det6d_nms");
@@ -399,13 +396,9 @@ DET6D_API int det6d_postprocess(int b, int p, int ncls, const float *cls, const 
                      pre_max > kPostMaxP ? kPostMaxP : pre_max, ws);
   hipLaunchKernelGGL(post_mask_kernel, dim3(det6d_divup(p, kMaskRows), b), dim3(256), 0, s, nms_thr, ws);
   const size_t lds = (size_t)p * ((p + 63) / 64) * sizeof(unsigned long long);
-  static bool big_lds_enabled = false;
-  if (lds > 48 * 1024 && !big_lds_enabled) {   // one-time opt-in for > 64 KB of dynamic LDS (160 KB per CU on gfx950)
-    hipError_t e = hipFuncSetAttribute((const void *)post_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       kPostMaxP * kPostCB * 8);
-    if (e != hipSuccess) { det6d_set_error("det6d_postprocess hipFuncSetAttribute", e); return DET6D_ELAUNCH; }
-    big_lds_enabled = true;
-  }
+  // opt-in for > 64 KB of dynamic LDS (160 KB per CU on gfx950), once per device; a limit the device refuses shows as the
+  // launch's error below
+  if (lds > 48 * 1024) DET6D_MAX_DYNAMIC_LDS(post_select_kernel, kPostMaxP * kPostCB * 8);
   hipLaunchKernelGGL(post_select_kernel, dim3(b), dim3(64), lds, s, p, boxes, post_max, ws, out_boxes, out_scores,
                      out_labels, out_index, out_count);
   return det6d_check_launch("det6d_postprocess");

@@ -200,8 +200,9 @@ def nms_mask(boxes, thresh, normal=False):
     return mask[:, :cb]
 
 
-def nms(boxes, thresh, normal=False):
-    """boxes (K,7) already sorted by descending score -> keep indices (int64)."""
+def nms(boxes, thresh, normal=False, with_mask=False):
+    """boxes (K,7) already sorted by descending score -> keep indices (int64); with_mask: (keep, the (K, ceil(K/64)) uint64
+    suppression rows the scan ran over, what nms_mask returns)."""
     boxes = _f(boxes)
     k = boxes.shape[0]
     cb = (k + 63) // 64
@@ -210,7 +211,8 @@ def nms(boxes, thresh, normal=False):
     num = _c_int(0)
     fn = lib().det6d_oracle_nms_normal if normal else lib().det6d_oracle_nms
     fn(k, _pf(boxes), _c_float(thresh), mask.ctypes.data_as(_up), keep.ctypes.data_as(_lp), ctypes.byref(num))
-    return keep[:num.value].copy()
+    keep = keep[:num.value].copy()
+    return (keep, mask[:k * cb].reshape(k, cb)) if with_mask else keep
 
 
 def nms_from_iou(iou, thresh):

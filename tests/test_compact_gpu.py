@@ -452,3 +452,31 @@ def test_rows_lds_limit_is_set_on_every_device(oracle_ops):
             assert fused.mlp_rows_eligible(480, [spec])
             fused.mlp_rows(dev(x), 0, [spec])
             np.testing.assert_array_equal(out.cpu().numpy(), ref)
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two devices")
+def test_nms_lds_limit_is_set_on_every_device(oracle_ops):
+    """csrc/iou3d_nms.hip: the same for the two NMS launches above the 64 KB default of dynamic LDS.  det6d_postprocess at 1024
+    candidates per scene stages 1024 x 16 words = 128 KB for its scan; det6d_nms at K = 1024 stages 768 rows + the removal words
+    = 98 432 bytes.  First on device 0, then on device 1 (a process-wide "limit is set" flag left it at the default there);
+    == the oracle on both"""
+    from de6d_amd.ops import fused
+    from tests.util import random_boxes
+    b, p, k = 2, 1024, 1024
+    rng = np.random.default_rng(1024)
+    boxes9 = np.zeros((b * p, 9), np.float32)
+    boxes9[:, :7] = random_boxes(5, b * p, spread=60.0)
+    boxes9[:, 7] = rng.normal(size=b * p) * 0.1
+    cls = (rng.normal(size=(b * p, 1)) * 2 + 1).astype(np.float32)
+    ref_post = oracle_ops.postprocess(cls, boxes9, b, 0.0, 4096, 100, 0.1)
+    assert ref_post[4].min() > 0
+    boxes = random_boxes(k, k, 45.0)
+    ref_keep = oracle_ops.nms(boxes, 0.1)
+    assert 0 < len(ref_keep) < k
+    for d in (0, 1):
+        with torch.cuda.device(d):
+            got = fused.postprocess(dev(cls), dev(boxes9), b, 0.0, 4096, 100, 0.1)
+            for g, r in zip(got, ref_post):
+                np.testing.assert_array_equal(g.cpu().numpy(), r)
+            keep, num = fused.nms_device(dev(boxes), 0.1)
+            np.testing.assert_array_equal(keep[:int(num.item())].cpu().numpy(), ref_keep)

@@ -131,6 +131,110 @@ def test_centre_grad_and_vote_backward(m, ns):
     np.testing.assert_array_equal(got[:4, :3] != 0, [[True] * 3, [False] * 3, [False, True, True], [True, False, True]])
 
 
+# ---- 1b. beyond the launch cap -------------------------------------------------------------------------------------------
+# group_backward.hip launches at most 2048 workgroups of 256 lanes and walks the rest by grid-stride loops.  Every kernel once
+# with more lanes than that, by a ragged rest, the lanes per row / group placed so that the wrap falls inside one.
+CAP = 2048 * 256
+
+
+def beyond_cap(lanes, inner):
+    return CAP < lanes < 2 * CAP and lanes % CAP != 0 and CAP % inner != 0
+
+
+def test_gather_beyond_the_launch_cap():
+    from de6d_amd.ops import group_backward as op
+    m, ns, k = 1100, 16, 67
+    rng = np.random.default_rng(m + ns)
+    cnt, idx = model.padded_query(rng, B, N, m, ns, counts=(0, 1, ns // 2, ns, ns))
+    rows = B * m * ns
+    ctr = np.full((B, m, 4), SENTINEL, F32)
+    ctr[..., :3] = rng.normal(size=(B, m, 3)).astype(F32)
+    ldout = round4(k) + 4
+    assert beyond_cap(rows * (ldout // 4), ldout // 4)                    # 633 600 float4 lanes
+    assert rows * ldout > 2 * CAP and (rows * ldout) % CAP and CAP % ldout   # 2 534 400 scalar lanes: a fifth, ragged trip
+    for ldp in (round4(k) + 4, k + 2 + (k & 1)):
+        pts = np.full((B, N, ldp), SENTINEL, F32)
+        pts[..., :k] = rng.normal(size=(B, N, k)).astype(F32)
+        out = torch.full((rows + 1, ldout), SENTINEL, dtype=torch.float32, device='cuda')
+        op.group_gather(dev(pts), dev(idx), dev(ctr), k=k, out=out[:rows])
+        got = out.cpu().numpy()
+        want = model.group_gather(pts, idx, ctr, k=k, ldout=ldout)
+        np.testing.assert_array_equal(got[:rows].astype(np.float64), want, err_msg='gather ldp=%d' % ldp)
+        assert (got[rows] == SENTINEL).all() and not got[:rows, k:].any()
+
+
+@pytest.mark.parametrize("c,vec", ((1020, True), (251, False)))
+def test_pool_backward_beyond_the_launch_cap(c, vec):
+    """four channels per lane (255 lanes per group) and one (251): the empty first ball, the designed tie and the non-positive
+    channel of test_gather_and_pool_backward_equal_the_model in the last group"""
+    from de6d_amd.ops import group_backward as op
+    m, ns = 1100, 4
+    rng = np.random.default_rng(c)
+    cnt, idx = model.padded_query(rng, B, N, m, ns, counts=(0, 1, ns // 2, ns, ns))
+    rows, groups = B * m * ns, B * m
+    ldy, lddz, ldg, gcol0 = (round4(c) + 4, round4(c) + 4, round4(c) + 8, 4) if vec else (c + 3, c + 1, c + 5, 3)
+    assert vec == (c % 4 == 0 and ldy % 4 == 0 and lddz % 4 == 0)
+    per_group = c // 4 if vec else c
+    assert beyond_cap(groups * per_group, per_group)
+    table = np.maximum(rng.normal(size=(B, N, c)), 0.0).astype(F32)
+    r0, lo = (groups - 1) * ns, (ns - 1) // 2
+    y = np.full((rows, ldy), SENTINEL, F32)
+    y[:, :c] = table[np.arange(B)[:, None, None], idx].reshape(rows, c)
+    y[r0:r0 + ns, 0] = 0.25
+    y[r0 + lo, 0] = y[r0 + ns - 1, 0] = 9.0                              # two distinct slots hold the positive maximum
+    y[r0:r0 + ns, c - 1] = -np.arange(ns, dtype=F32)                      # an all-non-positive channel (maximum 0 at slot 0)
+    cnt.reshape(-1)[-1] = ns                                              # the designed group is a full ball
+    assert cnt.reshape(-1)[0] == 0
+    g = np.full((groups, ldg), SENTINEL, F32)
+    g[:, gcol0:gcol0 + c] = rng.normal(size=(groups, c)).astype(F32) + 3.0
+    dz = torch.full((rows, lddz), SENTINEL, dtype=torch.float32, device='cuda')
+    op.pool_backward(dev(y), dev(cnt), dev(g), ns, c, gcol0=gcol0, dz=dz)
+    got = dz.cpu().numpy()
+    want = model.pool_backward(y, cnt, g, ns, c, gcol0=gcol0)
+    np.testing.assert_array_equal(got[:, :c].astype(np.float64), want)
+    assert (got[:, c:] == SENTINEL).all()
+    assert not got[:ns, :c].any()                                         # the empty ball passes nothing
+    assert got[r0 + lo, 0] == g[-1, gcol0] and got[r0 + ns - 1, 0] == 0   # the lowest slot won
+    assert not got[r0:r0 + ns, c - 1].any()
+
+
+def test_centre_grad_and_vote_backward_beyond_the_launch_cap():
+    from de6d_amd.ops import group_backward as op
+    groups, ns = 175001, 3
+    rng = np.random.default_rng(groups)
+    rows = groups * ns
+    assert beyond_cap(groups * 3, 3)
+    for integers in (True, False):
+        dx = np.full((rows, 5), SENTINEL, F32)
+        dx[:, :3] = rng.integers(-3, 4, size=(rows, 3)).astype(F32) if integers else rng.normal(size=(rows, 3)).astype(F32)
+        out = torch.full((groups, 4), SENTINEL, dtype=torch.float32, device='cuda')
+        op.centre_grad(dev(dx), ns, out=out)
+        got = out.cpu().numpy()
+        assert (got[:, 3] == SENTINEL).all()
+        want = model.centre_grad(dx, ns)
+        if integers:
+            np.testing.assert_array_equal(got[:, :3].astype(np.float64), want)
+        else:
+            lim = (ns + 2) * U * np.abs(dx[:, :3].astype(np.float64)).reshape(groups, ns, 3).sum(1)
+            err = np.abs(got[:, :3].astype(np.float64) - want)
+            worst = float((err / np.maximum(lim, 1e-300)).max())
+            print('group_backward centre_grad groups=%d ns=%d: largest ratio to the bound %.4f' % (groups, ns, worst))
+            assert np.isfinite(got[:, :3]).all() and (err <= lim).all(), worst
+    n = groups                                                            # vote_backward: as many rows
+    off = np.array([[0.0, 2.9, -1.9], [3.5, -3.5, 2.5], [np.nan, 3.0, -2.0], [-3.0, np.nan, 2.0]], F32)
+    off = np.concatenate([off, (rng.normal(size=(n - 4, 3)) * 2.5).astype(F32)])
+    offb = np.full((n, 4), SENTINEL, F32)
+    offb[:, :3] = off
+    dv = np.full((n, 5), SENTINEL, F32)
+    dv[:, :3] = rng.normal(size=(n, 3)).astype(F32)
+    out = torch.full((n, 4), SENTINEL, dtype=torch.float32, device='cuda')
+    op.vote_backward(dev(offb), RANGE, dev(dv), out=out)
+    got = out.cpu().numpy()
+    assert (got[:, 3] == SENTINEL).all()
+    np.testing.assert_array_equal(got[:, :3].astype(np.float64), model.vote_backward(off, RANGE, dv))
+    np.testing.assert_array_equal(got[:4, :3] != 0, [[True] * 3, [False] * 3, [False, True, True], [True, False, True]])
+
+
 # ---- 2. determinism -----------------------------------------------------------------------------------------------------
 def folded(rng, krows, k, cout):
     w = np.zeros((krows, round4(cout)), F32)

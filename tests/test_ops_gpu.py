@@ -164,6 +164,79 @@ def test_iou_and_nms_bit_exact(ext, oracle_ops, k):
     np.testing.assert_array_equal(kd[:int(nd.item())].cpu().numpy(), oracle_ops.nms(boxes, 0.1))
 
 
+def nms_chunk_rows(k):
+    """rows of the suppression matrix the greedy scan stages per chunk (csrc/iou3d_nms.hip: run_nms), RESTATED here from its
+    rule — as many rows of ceil(K / 64) words as fit 96 KB of LDS, K at the most — and not asked of the library"""
+    return max(1, min(k, 96 * 1024 // (8 * ((k + 63) // 64))))
+
+
+def nms_suppressors(mask, keep, k):
+    """from the oracle's suppression rows and keep list: (first, last) kept box whose row holds box j's bit, -1 where none"""
+    bits = np.unpackbits(mask[keep].view(np.uint8), axis=1, bitorder='little')[:, :k].astype(bool)      # (kept, K)
+    bits &= np.arange(k)[None, :] > keep[:, None]          # the scan reads a row from its own box on (the oracle fills the row)
+    hit = bits.any(axis=0)
+    first = np.where(hit, keep[bits.argmax(axis=0)], -1)
+    last = np.where(hit, keep[len(keep) - 1 - bits[::-1].argmax(axis=0)], -1)
+    return first, last
+
+
+@pytest.mark.parametrize("k,spread", [(704, 38.0), (705, 38.0), (877, 42.0), (878, 42.0), (1024, 45.0), (1500, 50.0), (4290, 90.0)])
+def test_nms_beyond_one_chunk_of_suppression_rows(ext, oracle_ops, k, spread):
+    """det6d_nms / det6d_nms_normal on both sides of the three sizes at which the greedy scan changes (csrc/iou3d_nms.hip:
+    run_nms, nms_greedy_kernel): K = 705 is the first launch above the 64 KB default of dynamic LDS (704: 62 040 bytes, 705:
+    67 776), K = 878 the first scan in two chunks of staged rows (removal words carried from one chunk into the next), K > 4096
+    gives a lane more than one removal word (the `w += 64` loops take a second trip).  Keep lists == the oracle's, through
+    nms_gpu, nms_normal_gpu and fused.nms_device.
+
+    That a case bites is asserted on the ORACLE's result, before the GPU runs:
+      * K >= 878: removed boxes whose first suppressing keeper lies in an earlier chunk, and among them boxes with NO suppressing
+        keeper in their own chunk — a scan that forgot the removal words at a chunk boundary keeps the lowest such box, and
+        one that staged another number of rows than it indexes reads another box's row for it;
+      * K = 4290: kept and removed boxes from index 4096 on (words 64 .. 67), and among the removed a box all of whose suppressing
+        keepers lie 64 words or more below its own word: only the second trip of the update loop ORs their rows into it."""
+    _, nm, fused = ext
+    boxes = random_boxes(k, k, spread)
+    boxes[3] = boxes[1]                     # identical boxes
+    boxes[4, 3:5] = 0.0                     # zero-area box
+    rows = nms_chunk_rows(k)
+    cb = (k + 63) // 64
+    lds = (cb + rows * cb) * 8
+    assert (lds > 64 * 1024) == (k >= 705) and lds <= 128 * 1024
+    assert ((k + rows - 1) // rows >= 2) == (k >= 878)
+    bd = dev(boxes)
+    for thr in (0.01, 0.3):
+        want, mask = oracle_ops.nms(boxes, thr, with_mask=True)
+        removed = np.setdiff1d(np.arange(k), want)
+        assert 0.1 * k <= len(want) <= 0.6 * k, (len(want), k)          # many kept AND many removed (12 .. 54 % are kept)
+        first, last = nms_suppressors(mask, want, k)
+        assert (first[want] == -1).all() and (first[removed] >= 0).all() and (last[removed] < removed).all()
+        carried = removed[first[removed] // rows < removed // rows]
+        only_carried = removed[last[removed] // rows < removed // rows]
+        far = removed[(last[removed] >> 6) + 64 <= (removed >> 6)]
+        print('nms K=%d thr=%.2f: kept %d, chunks of %d rows, first keeper in an earlier chunk %d, every keeper %d; from 4096 on '
+              'kept %d removed %d, every keeper 64 words below %d' % (k, thr, len(want), rows, len(carried), len(only_carried),
+                                                                      (want >= 4096).sum(), (removed >= 4096).sum(), len(far)))
+        if k >= 878:
+            assert len(carried) > 0 and len(only_carried) > 0
+        else:
+            assert len(carried) == 0
+        if k > 4096:
+            assert (want >= 4096).any() and (removed >= 4096).any() and len(far) > 0
+        keep = torch.full((k,), -1, dtype=torch.int64)
+        num = nm.nms_gpu(bd, keep, thr)
+        np.testing.assert_array_equal(keep[:num].numpy(), want)
+        assert (keep[num:] == -1).all()
+        kd, nd = fused.nms_device(bd, thr)
+        np.testing.assert_array_equal(kd[:int(nd.item())].cpu().numpy(), want)
+        want_n = oracle_ops.nms(boxes, thr, normal=True)
+        keep.fill_(-1)
+        num = nm.nms_normal_gpu(bd, keep, thr)
+        np.testing.assert_array_equal(keep[:num].numpy(), want_n)
+        assert (keep[num:] == -1).all()
+        kd, nd = fused.nms_device(bd, thr, normal=True)
+        np.testing.assert_array_equal(kd[:int(nd.item())].cpu().numpy(), want_n)
+
+
 @pytest.mark.parametrize("rows,k,n", [(256, 16, 16), (1000, 132, 64), (384, 260, 256), (128, 68, 32),
                                       (4096, 512, 1024), (77, 4, 3), (640, 36, 96)])
 def test_linear_rows_bit_exact(ext, oracle_ops, rows, k, n):
@@ -304,6 +377,37 @@ def test_postprocess_pair_filtered_mask_at_1024_candidates(ext, oracle_ops, p, k
         for g, r in zip(got, ref):
             np.testing.assert_array_equal(g.cpu().numpy(), r)
     assert ref[4].min() > 0
+
+
+def test_postprocess_cuts_at_pre_max_and_post_max(ext, oracle_ops):
+    """det6d_postprocess where both cuts bind (the 65536-point configuration: 1024 candidates per scene, NMS_PRE_MAXSIZE 512):
+    more than pre_max candidates pass the score threshold, so only the 512 best reach the NMS, and post_max = 7 cuts the
+    survivors.  The vote-like clusters of test_postprocess_pair_filtered_mask_at_1024_candidates (same draw order); all five
+    outputs == the oracle's.  That the cuts bind is asserted on the oracle's results."""
+    fused = ext[2]
+    b, p = 3, 1024
+    rng = np.random.default_rng(p * 7 + 8)
+    boxes = np.zeros((b * p, 9), np.float32)
+    boxes[:, :7] = random_boxes(3, b * p, spread=60.0)
+    centres = rng.uniform(-50, 50, (40, 2))
+    pick = rng.integers(0, 40, b * p)
+    boxes[:, 0] = centres[pick, 0] + rng.normal(size=b * p) * 0.7
+    boxes[:, 1] = centres[pick, 1] + rng.normal(size=b * p) * 0.7
+    boxes[:, 7] = rng.normal(size=b * p) * 0.1
+    cls = (rng.normal(size=(b * p, 1)) * 2 + 1).astype(np.float32)
+    passing = (oracle_ops.math_fn("sigmoid", cls).reshape(b, p) >= np.float32(0.1)).sum(axis=1)
+    assert (passing > 512).all() and (passing < p).all(), passing                      # 967, 978, 976
+    uncut = oracle_ops.postprocess(cls, boxes, b, 0.1, 4096, 100, 0.01)
+    for post_max in (100, 7):
+        ref = oracle_ops.postprocess(cls, boxes, b, 0.1, 512, post_max, 0.01)
+        if post_max == 100:
+            assert (ref[4] < post_max).all() and (ref[4] != uncut[4]).all(), (ref[4], uncut[4])   # 53, 54, 58 against 62, 65, 68
+            assert not np.array_equal(ref[3], uncut[3])
+        else:
+            assert (ref[4] == post_max).all()
+        got = fused.postprocess(dev(cls), dev(boxes), b, 0.1, 512, post_max, 0.01)
+        for g, r in zip(got, ref):
+            np.testing.assert_array_equal(g.cpu().numpy(), r)
 
 
 @pytest.mark.parametrize("n,m,sa,sb", [(16384, 700, (0.0, 0.2, 16), (0.2, 0.8, 32)), (4096, 1024, (0.0, 0.8, 16), (0.8, 1.6, 32)),
@@ -709,10 +813,13 @@ def test_fallback_kernels_via_env_switches(tmp_path):
     assert 'passed' in out.stdout
 
 
-@pytest.mark.parametrize("b,n,m,c", [(2, 16384, 4096, 64), (1, 300, 50, 3), (1, 2048, 16384, 5), (3, 1024, 4093, 7), (2, 5000, 512, 4)])
+@pytest.mark.parametrize("b,n,m,c", [(2, 16384, 4096, 64), (1, 300, 50, 3), (1, 2048, 16384, 5), (3, 1024, 4093, 7), (2, 5000, 512, 4),
+                                     (2, 1024, 4097, 5), (1, 3000, 8192, 1), (2, 2048, 6001, 64), (1, 1500, 16385, 3)])
 def test_three_interpolate_shapes(ext, oracle_ops, b, n, m, c):
-    """both forms of det6d_three_interpolate (channel rows staged in LDS when four of them fit 64 KB and n >= 1024, the plain
-    gather otherwise; odd m: unaligned rows) against the oracle, bit for bit"""
+    """both forms of det6d_three_interpolate (channel rows staged in LDS when four, two or one of them fit 64 KB and n >= 1024,
+    the plain gather otherwise; odd m: unaligned rows) against the oracle, bit for bit.  Two rows per workgroup (4096 < m <= 8192):
+    m = 4097 with five channels (unaligned rows, the last channel block half full), m = 8192 (exactly 64 KB), m = 6001 (odd);
+    m = 16385: one row too long for the LDS, the plain kernel at n >= 1024"""
     pn = ext[0]
     rng = np.random.default_rng(n + m)
     feats = rng.normal(size=(b, c, m)).astype(np.float32)
@@ -721,3 +828,111 @@ def test_three_interpolate_shapes(ext, oracle_ops, b, n, m, c):
     out = torch.empty((b, c, n), device="cuda")
     pn.three_interpolate_wrapper(b, c, m, n, dev(feats), dev(idx), dev(w), out)
     np.testing.assert_array_equal(out.cpu().numpy(), oracle_ops.three_interpolate(feats, idx, w))
+
+
+# ---- grid-stride second trips -------------------------------------------------------------------------------------------------
+# csrc/points.hip launches at most 8192 workgroups of 256 lanes; beyond that a lane walks further elements by a grid-stride
+# loop.  One case per kernel whose element count exceeds the cap by a ragged rest, the inner dimension placed so that the wrap
+# falls inside a row.
+POINTS_CAP = 8192 * 256
+U24 = 2.0 ** -24
+
+
+def scatter_sum64(index, terms, n):
+    """(float64 sum, float64 sum of magnitudes, count) of `terms` (..., L) scattered to `index` (L,) in [0, n)"""
+    lead = terms.shape[:-1]
+    flat = terms.reshape(-1, terms.shape[-1]).astype(np.float64)
+    total = np.stack([np.bincount(index, weights=row, minlength=n) for row in flat]).reshape(lead + (n,))
+    mag = np.stack([np.bincount(index, weights=np.abs(row), minlength=n) for row in flat]).reshape(lead + (n,))
+    return total, mag, np.bincount(index, minlength=n)
+
+
+def check_atomic_sum(name, got, total, mag, count):
+    """fp32 atomic adds in any order onto a zeroed element: every add rounds a partial sum of magnitude <= sum|terms| once
+    (relative 2^-24), a term that is itself a rounded product brings one more, second-order terms one more:
+    |got - sum64| <= (L_e + 2) * 2^-24 * sum|terms| with L_e the number of contributions.  Derived, not measured."""
+    lim = (count + 2) * U24 * mag
+    err = np.abs(got.astype(np.float64) - total)
+    ratio = float((err / np.maximum(lim, 1e-300)).max())
+    print('%s: contributions per element %d .. %d, largest ratio to the bound %.4f' % (name, count.min(), count.max(), ratio))
+    assert np.isfinite(got).all() and (err <= lim).all(), ratio
+    assert count.max() < 100 and count.min() >= 0
+
+
+def test_grid_stride_second_trip_of_the_forward_index_kernels(ext, oracle_ops):
+    pn, _, fused = ext
+    rng = np.random.default_rng(77)
+    # gather_points: 2 x 5 x 210 001 outputs
+    b, c, n, m = 2, 5, 300, 210001
+    assert POINTS_CAP < b * c * m < 2 * POINTS_CAP and (b * c * m) % POINTS_CAP and POINTS_CAP % m
+    pts = rng.normal(size=(b, c, n)).astype(np.float32)
+    idx = rng.integers(0, n, (b, m)).astype(np.int32)
+    out = torch.full((b, c, m), SENT, device="cuda")
+    pn.gather_points_wrapper(b, c, n, m, dev(pts), dev(idx), out)
+    np.testing.assert_array_equal(out.cpu().numpy(), oracle_ops.gather_points(pts, idx))
+    # group_points: 2 x 3 x 11 001 x 32
+    b, c, n, m, ns = 2, 3, 300, 11001, 32
+    assert POINTS_CAP < b * c * m * ns < 2 * POINTS_CAP and (b * c * m * ns) % POINTS_CAP and POINTS_CAP % (m * ns)
+    pts = rng.normal(size=(b, c, n)).astype(np.float32)
+    gidx = rng.integers(0, n, (b, m, ns)).astype(np.int32)
+    gout = torch.full((b, c, m, ns), SENT, device="cuda")
+    pn.group_points_wrapper(b, c, n, m, ns, dev(pts), dev(gidx), gout)
+    np.testing.assert_array_equal(gout.cpu().numpy(), oracle_ops.group_points(pts, gidx))
+    # three_interpolate, plain kernel (n < 1024 points per scene): 2 x 1051 x 999
+    b, c, m, n = 2, 1051, 50, 999
+    assert POINTS_CAP < b * c * n < 2 * POINTS_CAP and (b * c * n) % POINTS_CAP and POINTS_CAP % n
+    feats = rng.normal(size=(b, c, m)).astype(np.float32)
+    tidx = rng.integers(0, m, size=(b, n, 3)).astype(np.int32)
+    w = rng.uniform(0, 1, (b, n, 3)).astype(np.float32)
+    tout = torch.full((b, c, n), SENT, device="cuda")
+    pn.three_interpolate_wrapper(b, c, m, n, dev(feats), dev(tidx), dev(w), tout)
+    np.testing.assert_array_equal(tout.cpu().numpy(), oracle_ops.three_interpolate(feats, tidx, w))
+    # gather_rows: 2 x 30 001 rows of 35 of 37 columns into rows of 36
+    b, n, m, ld_in, ld_out, ncol = 2, 500, 30001, 37, 36, 35
+    assert POINTS_CAP < b * m * ncol < 2 * POINTS_CAP and (b * m * ncol) % POINTS_CAP and POINTS_CAP % ncol
+    rows_in = rng.normal(size=(b, n, ld_in)).astype(np.float32)
+    ridx = rng.integers(0, n, (b, m)).astype(np.int32)
+    rout = torch.full((b, m, ld_out), SENT, device="cuda")
+    fused.gather_rows(dev(rows_in), dev(ridx), ncol, rout)
+    got = rout.cpu().numpy()
+    np.testing.assert_array_equal(got[..., :ncol], oracle_ops.gather_rows(rows_in, ridx, ncol, ld_out)[..., :ncol])
+    assert (got[..., ncol:] == SENT).all()
+
+
+def test_grid_stride_second_trip_of_the_atomic_gradients(ext):
+    """gather_points_grad, group_points_grad, three_interpolate_grad beyond the launch cap: atomic adds, so the order of a sum is
+    free; against the float64 sum within check_atomic_sum's bound, some 30 contributions per element"""
+    pn = ext[0]
+    rng = np.random.default_rng(78)
+    # gather_points_grad: 2 x 5 x 210 001 terms onto 7000 points per (scene, channel)
+    b, c, n, m = 2, 5, 7000, 210001
+    assert POINTS_CAP < b * c * m < 2 * POINTS_CAP and (b * c * m) % POINTS_CAP and POINTS_CAP % m
+    go = rng.normal(size=(b, c, m)).astype(np.float32)
+    idx = rng.integers(0, n, (b, m)).astype(np.int32)
+    gp = torch.zeros((b, c, n), device="cuda")
+    pn.gather_points_grad_wrapper(b, c, n, m, dev(go), dev(idx), gp)
+    got = gp.cpu().numpy()
+    for bi in range(b):
+        check_atomic_sum('gather_points_grad scene %d' % bi, got[bi], *scatter_sum64(idx[bi], go[bi], n))
+    # group_points_grad: 2 x 3 x 11 001 x 32 terms onto 12 000 points
+    b, c, n, m, ns = 2, 3, 12000, 11001, 32
+    assert POINTS_CAP < b * c * m * ns < 2 * POINTS_CAP and (b * c * m * ns) % POINTS_CAP and POINTS_CAP % (m * ns)
+    ggo = rng.normal(size=(b, c, m, ns)).astype(np.float32)
+    gidx = rng.integers(0, n, (b, m, ns)).astype(np.int32)
+    ggp = torch.zeros((b, c, n), device="cuda")
+    pn.group_points_grad_wrapper(b, c, n, m, ns, dev(ggo), dev(gidx), ggp)
+    got = ggp.cpu().numpy()
+    for bi in range(b):
+        check_atomic_sum('group_points_grad scene %d' % bi, got[bi], *scatter_sum64(gidx[bi].reshape(-1), ggo[bi].reshape(c, m * ns), n))
+    # three_interpolate_grad: 2 x 3 x 350 003 outputs, three terms each (the fp32 product g * w), onto 35 000 points
+    b, c, n, m = 2, 3, 350003, 35000
+    assert POINTS_CAP < b * c * n < 2 * POINTS_CAP and (b * c * n) % POINTS_CAP and POINTS_CAP % n
+    tgo = rng.normal(size=(b, c, n)).astype(np.float32)
+    tidx = rng.integers(0, m, size=(b, n, 3)).astype(np.int32)
+    w = rng.uniform(0, 1, (b, n, 3)).astype(np.float32)
+    tgp = torch.zeros((b, c, m), device="cuda")
+    pn.three_interpolate_grad_wrapper(b, c, n, m, dev(tgo), dev(tidx), dev(w), tgp)
+    got = tgp.cpu().numpy()
+    for bi in range(b):
+        terms = tgo[bi].astype(np.float64)[:, :, None] * w[bi].astype(np.float64)[None]            # (c, n, 3): exact products
+        check_atomic_sum('three_interpolate_grad scene %d' % bi, got[bi], *scatter_sum64(tidx[bi].reshape(-1), terms.reshape(c, n * 3), m))

@@ -195,6 +195,12 @@ def lib():
     return _lib
 
 
+class SasaSegment(ctypes.Structure):
+    """det6d_ext_sasa_segment (include/det6d_ext.h)"""
+    _fields_ = [("coords", c_void_p), ("m", c_int), ("ld", c_int), ("xyz_col", c_int), ("weight", c_float),
+                ("scores", c_void_p), ("labels", c_void_p), ("d_scores", c_void_p)]
+
+
 #: libdet6d_hip_ext.so (include/det6d_ext.h): entry points without an oracle twin (INTEGRATION.md, "The extension library")
 EXT_LIB_PATH = os.path.join(_HERE, "csrc", "libdet6d_hip_ext.so")
 _EXT_SIGNATURES = {
@@ -215,12 +221,18 @@ _EXT_SIGNATURES = {
     "det6d_ext_group_pool_backward": [c_int, c_int, c_int, _P, c_int, _P, _P, c_int, c_int, _P, c_int, _P],
     "det6d_ext_group_centre_grad": [c_int, c_int, _P, c_int, _P, c_int, _P],
     "det6d_ext_vote_backward": [c_int, _P, c_int, c_float, c_float, c_float, _P, c_int, _P, c_int, _P],
+    "det6d_ext_points_in_boxes7": [c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P],
+    "det6d_ext_sasa_forward": [c_int, ctypes.POINTER(SasaSegment), c_int, c_int, _P, c_int, _P, c_int, c_int, c_float, c_float,
+                               _P, c_int64, _P, _P],
+    "det6d_ext_sasa_backward": [c_int, ctypes.POINTER(SasaSegment), c_int, c_int, _P, c_int, _P, c_int, c_int, c_float, c_float,
+                                _P, _P, c_int, _P],
 }
 #: every symbol include/det6d_ext.h declares (tests/test_ext_boundary.py checks the export table)
 EXT_EXPORTED_SYMBOLS = sorted(list(_EXT_SIGNATURES) + ["det6d_ext_version", "det6d_ext_last_error",
                                                           "det6d_ext_fps_features_workspace_bytes",
                                                           "det6d_ext_head_loss_workspace_bytes",
-                                                          "det6d_ext_linear_backward_workspace_bytes"])
+                                                          "det6d_ext_linear_backward_workspace_bytes",
+                                                          "det6d_ext_sasa_workspace_bytes"])
 _ext_lib = None
 
 
@@ -245,6 +257,8 @@ def ext_lib():
         handle.det6d_ext_head_loss_workspace_bytes.restype = c_int64
         handle.det6d_ext_linear_backward_workspace_bytes.argtypes = [c_int, c_int, c_int]
         handle.det6d_ext_linear_backward_workspace_bytes.restype = c_int64
+        handle.det6d_ext_sasa_workspace_bytes.argtypes = [c_int, ctypes.POINTER(SasaSegment), c_int]
+        handle.det6d_ext_sasa_workspace_bytes.restype = c_int64
         _ext_lib = handle
     return _ext_lib
 

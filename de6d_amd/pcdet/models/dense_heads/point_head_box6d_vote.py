@@ -30,8 +30,16 @@ the SA layer around the votes (ops.group_backward: VotePoints, GroupedChain; the
 their membership a constant), so that loss.backward() leaves .grad on every parameter of vote_layers, SA_module.mlps and the
 three stacks: the vote coordinates collect the loss's own d_vote and the d(new_xyz) of every radius group.  At a vote offset
 exactly on its clamp bound the whole gradient passes (torch's max / min backward passes half).
-The gradient with respect to the input points' features and coordinates (the backbone), BatchNorm with batch statistics and a
-training-mode forward() stay out of scope.
+The SASA loss (:146-155, :733-750, :772-775, :878-887 with loss_utils.py:418-547): with LOSS_CONFIG.LOSS_SASA_CONFIG
+(func, layer_weights, extra_width, set_ignore_flag) prepare_loss stores point_sasa_preds / point_sasa_labels, and
+get_sasa_layer_loss / get_loss add the layer-wise segmentation loss of the backbone's confidence scores (csrc/ext/sasa_loss.hip:
+two launches for the labels, two for the loss, one for its gradient).  prepare_loss(batch_dict, requires_grad=True, sasa=True)
+re-evaluates every confidence_mlp of the backbone from the rows of its level (constants), so that loss.backward() leaves .grad
+on the confidence layers' parameters — the layers that decide which points the head ever sees.  The labels are yaw-only
+(the reference passes gt_boxes[..., 0:7]), and an all-zero padding row of gt_boxes enlarged by extra_width is a small box at the
+origin, as in the reference.
+The gradient with respect to the input points' features and coordinates (the backbone's SA layers), BatchNorm with batch
+statistics and a training-mode forward() stay out of scope.
 Differences from the reference, all of them kept on purpose:
   * tb_dict values are 0-d device tensors, not Python floats: nothing is read on the host, the call can be captured;
   * labels are constants.  The reference has no detach at :310, so a gradient leaks from the encoded offset labels back into
@@ -43,10 +51,11 @@ Differences from the reference, all of them kept on purpose:
     (the reference passes [:, 0:7]);
   * the layer methods (get_*_layer_loss, generate_centerness_label, get_corner_loss_lidar) return values without a graph;
     the gradient flows through get_loss.
-Out of scope, raising NotImplementedError with the key's name: LOSS_SASA_CONFIG, AXIS_ALIGNED_IOU_LOSS_REGULARIZATION,
+Out of scope, raising NotImplementedError with the key's name: AXIS_ALIGNED_IOU_LOSS_REGULARIZATION, keys of LOSS_SASA_CONFIG
+other than func / layer_weights / extra_width / set_ignore_flag,
 LOSS_CLS FocalLoss / WeightedCrossEntropy, LOSS_REG WeightedL1Loss, code_weights, pred_velo, coders other than
 PointBinResidual6DCoder, use_mean_size.
-forward() in training mode, the set_ignore_flag=True variants, ASSIGN_METHOD: iou and the SASA labels (:328-385) are not
+forward() in training mode, the set_ignore_flag=True variants of the assign_* methods and ASSIGN_METHOD: iou (:328-385) are not
 implemented and raise.
 Parameters live under the reference's names (vote_layers, SA_module.mlps, shared_fc_layer,
 cls_layers, reg_layers) so reference checkpoints load unchanged."""
@@ -56,11 +65,17 @@ import torch.nn as nn
 from ...ops.pointnet2.pointnet2_batch import pointnet2_modules
 from ...ops.pointnet2.pointnet2_batch.pointnet2_modules import fold_sequential, neighbour_search, to_device
 from ...ops_backend import fused
-from ....ops import box_targets, group_backward, head_loss, mlp_backward
-from ...utils import box_coder_utils
+from ....ops import box_targets, group_backward, head_loss, mlp_backward, sasa_loss
+from ...utils import box_coder_utils, loss_utils
 
 
 class PointHeadBox6DVote(nn.Module):
+    #: the SASA loss: set by build_losses from LOSS_CONFIG.LOSS_SASA_CONFIG
+    enable_sasa = False
+    loss_point_sasa = None
+    #: set by Det6D.get_training_loss: LOSS_SASA_CONFIG.layer_weights is checked against the backbone's SA levels
+    num_sa_levels = None
+
     def __init__(self, num_class, input_channels, model_cfg, predict_boxes_when_training=False, **kwargs):
         super().__init__()
         self.model_cfg = model_cfg
@@ -310,8 +325,7 @@ class PointHeadBox6DVote(nn.Module):
             raise NotImplementedError("LOSS_CLS: %s is not implemented (WeightedBinaryCrossEntropyLoss[WithCenterness])" % loss_cls)
         if losses_cfg.get('LOSS_REG', None) != 'WeightedSmoothL1Loss':
             raise NotImplementedError("LOSS_REG: %s is not implemented (WeightedSmoothL1Loss)" % losses_cfg.get('LOSS_REG', None))
-        if losses_cfg.get('LOSS_SASA_CONFIG', None) is not None:
-            raise NotImplementedError("LOSS_SASA_CONFIG is not implemented")
+        loss_point_sasa = self._build_sasa_loss(losses_cfg.get('LOSS_SASA_CONFIG', None))
         if losses_cfg.get('AXIS_ALIGNED_IOU_LOSS_REGULARIZATION', False):
             raise NotImplementedError("AXIS_ALIGNED_IOU_LOSS_REGULARIZATION is not implemented")
         weights = losses_cfg.get('LOSS_WEIGHTS', None) or {}
@@ -335,7 +349,28 @@ class PointHeadBox6DVote(nn.Module):
             weights={k: weights[k] for k in head_loss.WEIGHT_KEYS if k in weights}, beta=reg_cfg.get('beta', 1.0 / 9.0),
             centerness_min=cls_cfg['centerness_min'] if cls_cfg is not None else 0.0,
             centerness_max=cls_cfg['centerness_max'] if cls_cfg is not None else 1.0)
+        self.enable_sasa = loss_point_sasa is not None
+        self.__dict__['loss_point_sasa'] = loss_point_sasa     # it has no parameters: kept out of the registered submodules
         return self._loss_spec
+
+    SASA_KEYS = ('func', 'layer_weights', 'extra_width', 'set_ignore_flag')
+
+    def _build_sasa_loss(self, sasa_cfg):
+        """LOSS_SASA_CONFIG (:146-155) -> loss_utils.PointSASALoss or None"""
+        if sasa_cfg is None:
+            return None
+        unknown = sorted(set(sasa_cfg) - set(self.SASA_KEYS))
+        if unknown:
+            raise NotImplementedError("LOSS_SASA_CONFIG: %s is not implemented (%s)" % (', '.join(unknown), ', '.join(self.SASA_KEYS)))
+        if sasa_cfg.get('layer_weights', None) is None:
+            raise KeyError("LOSS_SASA_CONFIG lacks layer_weights")
+        weights = list(sasa_cfg['layer_weights'])
+        if self.num_sa_levels is not None and len(weights) > self.num_sa_levels:
+            raise ValueError("LOSS_SASA_CONFIG.layer_weights lists %d layers, the backbone has %d" % (len(weights), self.num_sa_levels))
+        extra_width = sasa_cfg.get('extra_width', None)
+        return loss_utils.PointSASALoss(func=sasa_cfg.get('func', 'BCE'), layer_weights=weights,
+                                        extra_width=None if extra_width is None else list(extra_width),
+                                        set_ignore_flag=bool(sasa_cfg.get('set_ignore_flag', False)))
 
     def _loss_inputs(self):
         if self._loss_spec is None:
@@ -351,7 +386,7 @@ class PointHeadBox6DVote(nn.Module):
         spec, tensors = self._loss_inputs()
         return head_loss.forward(spec, *(t.detach().contiguous() for t in tensors), per_point=True)
 
-    def prepare_loss(self, batch_dict, requires_grad=False, towers=False, head=False):
+    def prepare_loss(self, batch_dict, requires_grad=False, towers=False, head=False, sasa=False, sa_modules=None):
         """Fills forward_ret_dict with what the reference's training forward puts there (:823-876), for the batch_dict an eval
         forward returned plus batch_dict['gt_boxes'] (B, M, 9 + 1): the five labels of assign_training_targets,
         point_candidate_coords and point_vote_coords as (N, 3), beside the predictions forward() left.
@@ -365,13 +400,26 @@ class PointHeadBox6DVote(nn.Module):
         (xyz, rows, cand_rows): vote_layers, the clamp, the ball queries around the votes (constants) and SA_module.mlps.
         point_vote_coords is then the (N, 3) view of the re-evaluated votes, a non-leaf in which the loss's d_vote and the SA
         layer's d(new_xyz) add up, and point_pooled_features the re-evaluated tensor — all of them the bits of the eval
-        forward.  backward() leaves .grad on every parameter of the head; the backbone gets nothing."""
+        forward.  backward() leaves .grad on every parameter of the head; the backbone gets nothing.
+        With LOSS_SASA_CONFIG, point_sasa_preds (the backbone's point_scores_list; leaves with requires_grad=True) and
+        point_sasa_labels (:878-887) are stored as well.  sasa=True (with sa_modules = the backbone's SA_modules, which
+        Det6D.get_training_loss passes) re-evaluates every weighted level's confidence_mlp from that level's rows — a constant:
+        nothing flows into the aggregated features — with a graph to its parameters and stores those scores, the bits of the
+        eval forward, instead: backward() then leaves .grad on every parameter of those confidence_mlp stacks and on nothing
+        else of the backbone.  The rows are not kept by the inference forward (it is left exactly as it is): the SA layers up
+        to the last weighted level run again, without a graph, at the centres the forward sampled (forward_rows with new_xyz:
+        the forward's own kernels, the same bits) and the rows are stored as point_sasa_rows.  Combines freely with towers /
+        head."""
         ret = self.forward_ret_dict
         if ret is None or 'point_reg_preds' not in ret:
             raise RuntimeError("prepare_loss needs the forward_ret_dict of an eval forward")
         towers = towers or head
-        if towers and self.training:
+        if (towers or sasa) and self.training:
             raise RuntimeError("the HIP head folds BatchNorm: call .eval() first")
+        if self._loss_spec is None:
+            self.build_losses(self.model_cfg.get('LOSS_CONFIG', None))
+        if sasa and not self.enable_sasa:
+            raise RuntimeError("prepare_loss(sasa=True) needs LOSS_CONFIG.LOSS_SASA_CONFIG")
         if head:
             for key in ('xyz', 'rows', 'cand_rows'):
                 if key not in ret:
@@ -403,7 +451,84 @@ class PointHeadBox6DVote(nn.Module):
                           ((self.shared_fc_layer, 'shared'), (self.cls_layers, 'cls'), (self.reg_layers, 'reg'))]
                 cls, reg = mlp_backward.folded_chain(pooled.view(-1, pooled.shape[-1]), chains[0], chains[1:], k0=k0)
             ret['point_cls_preds'], ret['point_reg_preds'] = cls, reg
+        if self.enable_sasa:
+            ret.pop('point_sasa_preds', None)      # let go of the previous step's graph before the new one is built (see head=True)
+            ret.update(self._prepare_sasa(batch_dict, requires_grad, sasa, sa_modules))
         return ret
+
+    def _prepare_sasa(self, batch_dict, requires_grad, reevaluate, sa_modules):
+        """point_sasa_preds and point_sasa_labels of forward_ret_dict (:878-887)"""
+        scores = list(batch_dict['point_scores_list'])
+        spec = self.loss_point_sasa.spec
+        n = len(spec.layer_weights)
+        if n > len(scores):
+            raise ValueError("LOSS_SASA_CONFIG.layer_weights lists %d layers, the backbone has %d" % (n, len(scores)))
+        out = {}
+        if reevaluate:
+            if sa_modules is None:
+                raise RuntimeError("prepare_loss(sasa=True) needs sa_modules, the backbone's SA_modules (Det6D.get_training_loss "
+                                   "passes them)")
+            live = [i for i in range(n) if not spec.skipped(i, scores)]
+            level_rows = self._level_rows(batch_dict, sa_modules, max(live) + 1 if live else 0)
+            for i in live:
+                sa, rows = sa_modules[i], level_rows[i]
+                b, m, ld = rows.shape
+                with torch.set_grad_enabled(requires_grad):
+                    chain = mlp_backward.folded_params(sa.confidence_mlp, sa._prepare(rows.device)['conf'], k_offset=3)
+                    scores[i], = mlp_backward.folded_chain(rows.view(b * m, ld), chain)
+            out['point_sasa_rows'] = level_rows + [None] * (len(scores) - len(level_rows))
+        else:
+            scores = [None if s is None else s.detach().requires_grad_(requires_grad) for s in scores]
+        labels = self.loss_point_sasa(batch_dict['point_coords_list'], scores, batch_dict['gt_boxes'])
+        out.update({'point_sasa_preds': scores, 'point_sasa_labels': labels})
+        return out
+
+    @staticmethod
+    @torch.no_grad()
+    def _level_rows(batch_dict, sa_modules, levels):
+        """the rows [xyz | aggregated features | pad] (B, M, ld) of the first `levels` SA levels, as the eval forward computed
+        them: the points packed again and every SA layer run again at the centres the forward sampled"""
+        if levels == 0:
+            return []
+        b = batch_dict['batch_size']
+        points = batch_dict['points'].contiguous()
+        ld = pointnet2_modules.rows_ld(points.shape[1] - 4)
+        rows, xyz = fused.pack_points(points, ld)
+        rows, xyz = rows.view(b, -1, ld), xyz.view(b, -1, 3)
+        coords = batch_dict['point_coords_list']
+        out = []
+        for i, sa in enumerate(list(sa_modules)[:levels]):
+            if sa.training:
+                raise RuntimeError("the HIP set-abstraction path folds BatchNorm: call .eval() first")
+            if sa.aggregation_mlp is None:
+                raise NotImplementedError("prepare_loss(sasa=True): an SA level without an aggregation MLP has no rows to re-evaluate")
+            centres = coords[i][:, 1:4].reshape(b, -1, 3).contiguous()
+            xyz, rows, _ = sa.forward_rows(xyz, rows, new_xyz=centres)
+            out.append(rows)
+        return out
+
+    def get_sasa_layer_loss(self, tb_dict=None):
+        """:733-750 -> (point_loss_sasa or None, tb_dict): two launches on the labels prepare_loss stored, and one more when the
+        loss's backward() runs; (None, None) without LOSS_SASA_CONFIG or when every layer is skipped.
+        tb_dict['point_loss_sasa_layer_%d'] and tb_dict['point_loss_sasa'] are 0-d device tensors"""
+        if self._loss_spec is None:
+            self.build_losses(self.model_cfg.get('LOSS_CONFIG', None))
+        if not self.enable_sasa:
+            return None, None
+        ret = self.forward_ret_dict
+        if ret is None or 'point_sasa_labels' not in ret:
+            raise RuntimeError("the loss reads forward_ret_dict: call prepare_loss(batch_dict) after an eval forward")
+        spec = self.loss_point_sasa.spec
+        preds, labels = ret['point_sasa_preds'], ret['point_sasa_labels']
+        if all(spec.skipped(i, preds) for i in range(len(spec.layer_weights))):
+            return None, None
+        loss, sums = sasa_loss.SasaLoss.apply(spec, None, None, labels, *preds)
+        tb_dict = {} if tb_dict is None else tb_dict
+        for i in range(len(spec.layer_weights)):
+            if labels[i] is not None:
+                tb_dict['point_loss_sasa_layer_%d' % i] = sums[4 * i]
+        tb_dict['point_loss_sasa'] = sums[-1]
+        return loss, tb_dict
 
     def _reevaluate_votes(self, ret):
         """vote_layers -> clamp -> ball queries -> SA_module.mlps -> max-pool, dense and layer by layer, with a graph to the
@@ -470,4 +595,8 @@ class PointHeadBox6DVote(nn.Module):
         tb_dict.update({'point_loss_vote': sums[head_loss.VOTE], 'point_loss_cls': sums[head_loss.CLS],
                         'point_loss_box': sums[head_loss.BOX], 'vote_loss_reg': sums[head_loss.VOTE],
                         'point_pos_num': sums[head_loss.N_POS]})
+        loss_sasa, tb_sasa = self.get_sasa_layer_loss()
+        if loss_sasa is not None:
+            tb_dict.update(tb_sasa)
+            loss = loss + loss_sasa
         return loss, tb_dict

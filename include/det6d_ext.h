@@ -278,6 +278,81 @@ int det6d_ext_group_centre_grad(int groups, int ns, const float *dx, int lddx, f
 int det6d_ext_vote_backward(int rows, const float *off, int ldoff, float rx, float ry, float rz, const float *dvote, int lddvote,
                             float *doff, int lddoff, det6d_stream_t stream);
 
+/* ------------------------------------------------------------------ SASA loss ---------- */
+
+/* The reference's yaw-only roiaware_pool3d_utils.points_in_boxes_gpu (roiaware_pool3d_kernel.cu:16-36, :313-336).
+ * Point layouts are those of det6d_ext_points_in_boxes9.  boxes (b, m, ld_boxes >= 7): columns 0 .. 6 are
+ * [x, y, z, dx, dy, dz, rz] and nothing else is read (the 9 + 1 column gt_boxes go in unsliced: ry and rx take no part);
+ * extra_width (3 floats or NULL = zeros) is added to dx, dy, dz.
+ * box_idx[r] = the LOWEST index of a box of the row's scene that contains the point, -1 if none — the reference's loop breaks at
+ * its first hit.  det6d_ext_points_in_boxes9 takes the HIGHEST index.
+ * Arithmetic, in fp32, every operation rounded once, nothing contracted:
+ *   per box: (s, c) = d6_sincosf(-rz) (det6d_math.h); h_k = 0.5f * (d_k + extra_k); g_x = h_x + 1e-5f, g_y = h_y + 1e-5f;
+ *   per pair: u = x - cx, v = y - cy; lx = u * c + v * (-s); ly = u * s + v * c;
+ *   inside iff fabsf(z - cz) <= h_z and fabsf(lx) < g_x and fabsf(ly) < g_y.
+ * A NaN coordinate, centre, angle or size is outside (every comparison is written so that a NaN fails it; the reference's
+ * z test alone, `fabsf(z - cz) > dz / 2` means outside, would let a NaN z pass).  There is NO "degenerate boxes contain nothing"
+ * rule: a zero-sized box still contains the points within the margin of its centre line, and an all-zero padding row enlarged
+ * by extra_width is a small box at the origin, as in the reference.  (The reference forms h + margin in double; a point within
+ * rounding distance of a face may fall on the other side.)
+ * Limits: those of det6d_ext_points_in_boxes9 with 7 <= ld_boxes.  With n_points == 0, b == 0 or m == 0 nothing is launched and
+ * nothing is written. */
+int det6d_ext_points_in_boxes7(int n_points, const float *points, int ld_points, int xyz_col, int bs_col, int n_per_scene,
+                               int b, int m, const float *boxes, int ld_boxes, const float *extra_width, int *box_idx,
+                               det6d_stream_t stream);
+
+/* PointSASALoss (loss_utils.py:418-547): the layer-wise foreground / background labels of the backbone's sampled points, the
+ * loss of the confidence scores against them and its gradient, for all layers and scenes at once.
+ * Executable model: tests/models/sasa.py.
+ * A layer is a segment: coords (b, m, ld) dense, the coordinates in columns xyz_col .. xyz_col + 2 (the scene of row r is r / m);
+ * scores (b * m) logits; weight = layer_weights[i].  A segment whose scores is NULL or whose weight is 0 is SKIPPED (the
+ * reference's None entries): it has no rows, its labels are not computed, nothing of it is read or written, and its entries of
+ * `sums` are zero.  `segments` is an array in HOST memory, read during the call.
+ * boxes, extra_width: as det6d_ext_points_in_boxes7 reads them, shared by all segments; in(p, e) = p lies in some box of its
+ * scene enlarged by e.
+ *   label = in(p, extra) ? 1 : 0                                   without DET6D_EXT_SASA_IGNORE (extra_width NULL: zeros);
+ *   label = in(p, 0) ? 1 : in(p, extra) ? -1 : 0                   with DET6D_EXT_SASA_IGNORE, the reference's set_ignore_flag
+ *                                                                  (needs extra_width).
+ * With z = [label > 0], bce = max(x, 0) - x z + log1p(exp(-|x|)), p = sigmoid(x):
+ *   l = bce                                                                        func = DET6D_EXT_SASA_BCE
+ *   l = (z alpha + (1 - z)(1 - alpha)) * pt^gamma * bce, pt = z (1 - p) + (1 - z) p          DET6D_EXT_SASA_FOCAL
+ *   sums[4 i + 0] = weight_i * sum_{label >= 0} l / max(norm_i, 1), sums[4 i + 1] = norm_i = #(label >= 0),
+ *   sums[4 i + 2] = #(label > 0), sums[4 i + 3] = #(label < 0); sums[4 n_segments] = the sum of the layers' losses (fp32 adds
+ *   in layer order from 0).  sums holds 4 n_segments + 1 floats.
+ * Reduction: slabs of DET6D_EXT_SASA_SLAB rows that never straddle a segment, shuffles over the wave, LDS over the waves, one
+ * record per slab in `workspace`, added per segment in slab order (in double) by a final launch: the same inputs give the same
+ * bits.  No floating-point atomics.  Two launches; with no rows (no segment, b == 0, every segment skipped or empty) nothing
+ * is launched and nothing written.
+ * forward: segment.labels (b * m) int64, or NULL, receives the labels; d_scores is not read.  With
+ *   DET6D_EXT_SASA_LABELS_GIVEN segment.labels is READ instead (PointSASALoss.loss_forward on labels the caller holds): no
+ *   coords, boxes or extra_width are read, and labels must not be NULL for a segment that is not skipped.
+ * backward: one launch; d_scores[r] = grad_loss[i * grad_stride] * weight_i * (1.0f / max(norm_i, 1)) * dl/dx, exactly 0 where
+ *   label < 0.  `sums` is what the forward wrote for the same inputs; grad_loss lives in DEVICE memory: ONE float, the upstream
+ *   gradient of the total (grad_stride 0), or one per layer, grad_stride floats apart (4: the layout of `sums`; 0 .. 4).
+ *   segment.labels, where not NULL, is READ instead of computing the labels again (coords and boxes are then not read for
+ *   that segment), with or without DET6D_EXT_SASA_LABELS_GIVEN.
+ * Limits: 0 <= n_segments <= 8, 0 <= b <= 4096, 0 <= m <= 1024 boxes, 7 <= ld_boxes <= 1024, per segment 0 <= m,
+ * 3 <= ld <= 1024, 0 <= xyz_col <= ld - 3, a finite weight; at most 2^24 rows in all; alpha and gamma finite, gamma >= 0;
+ * ws_bytes >= det6d_ext_sasa_workspace_bytes(n_segments, segments, b) (-1 for arguments out of range). */
+enum { DET6D_EXT_SASA_SLAB = 256, DET6D_EXT_SASA_MAX_SEGMENTS = 8 };
+enum { DET6D_EXT_SASA_BCE = 0, DET6D_EXT_SASA_FOCAL = 1 };                                           /* func */
+enum { DET6D_EXT_SASA_IGNORE = 1, DET6D_EXT_SASA_LABELS_GIVEN = 2 };                                 /* flags */
+typedef struct det6d_ext_sasa_segment {
+  const float *coords;
+  int m, ld, xyz_col;
+  float weight;
+  const float *scores;
+  long long *labels;
+  float *d_scores;
+} det6d_ext_sasa_segment;
+long long det6d_ext_sasa_workspace_bytes(int n_segments, const det6d_ext_sasa_segment *segments, int b);
+int det6d_ext_sasa_forward(int n_segments, const det6d_ext_sasa_segment *segments, int b, int m, const float *boxes, int ld_boxes,
+                           const float *extra_width, int flags, int func, float alpha, float gamma, void *workspace,
+                           long long ws_bytes, float *sums, det6d_stream_t stream);
+int det6d_ext_sasa_backward(int n_segments, const det6d_ext_sasa_segment *segments, int b, int m, const float *boxes, int ld_boxes,
+                            const float *extra_width, int flags, int func, float alpha, float gamma, const float *sums,
+                            const float *grad_loss, int grad_stride, det6d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
